@@ -1,8 +1,18 @@
 #!/usr/bin/env python
 """Benchmark: env-steps/s of the batched gym-TD step on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does what the headline figure needs: set-up and burn-in, W warm-up steps, the
+K timed steps, then the JSON line.  ``--full`` adds the legs that take runs of their own
+after it, the CPU baselines (``cpu_baseline``, ``cpu_baseline_python``: ``--cpu-seconds``,
+``--py-cpu-seconds``, ``--no-cpu-baseline``).  ``--dump-outputs DIR`` writes what the last
+timed step returned to its caller -- obs, reward, done and, where the engine writes them,
+the info arrays -- as ``DIR/<name>.npy`` (float32, float64 where the engine's array is);
+an array above its share of the 64 MB is cut to a fixed, seeded sample of boards, listed
+in ``DIR/<name>_boards.npy``.  Seeds, actions and burn-in depend on the arguments alone,
+so two builds run with the same arguments can be compared array for array.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (``torch.distributed.run`` as a child process, before anything touches the GPU) and
@@ -36,8 +46,8 @@ dispatch of every k-th launch of the timed region on the launch stream -- the
 timestamps rocprofv3's kernel trace reports; k from the warm-up's step time,
 ``event_every`` -- and the algorithmic bytes per launch;
 ``traffic`` is the PMC-measured HBM bytes per launch of the same kernel build at
-the same boards per GPU, with its source, or null) and ``cpu_baseline`` (the C
-restatement oracle/td_cpu.c on this host's cores, rank 0, N=1;
+the same boards per GPU, with its source, or null) and, with ``--full``,
+``cpu_baseline`` (the C restatement oracle/td_cpu.c on this host's cores, rank 0, N=1;
 ``cpu_baseline_python`` times the Python restatement the same way).
 """
 import argparse
@@ -219,6 +229,53 @@ def measured_traffic(workload, boards, kernel, obs_alloc, path=None):
             workload, boards, rec.get("round", "?"), rec["kernel_src"], obs_alloc)
 
 
+# --------------------------------------------------------------------------- outputs
+# What td_step hands its caller (TDEngine.step's obs / reward / done, and the info arrays of
+# engines created with info=True), by TDEngine attribute name.
+OUTPUT_NAMES = ("obs", "reward", "done", "win", "allow_next", "cooldowns", "ep_return", "ep_len",
+                "real_def", "fail_def", "real_atk", "fail_atk")
+DUMP_OBS_BYTES = 32 << 20  # the observation's share of --dump-outputs' 64 MB
+DUMP_ARRAY_BYTES = 1 << 20  # every other array's (11 at most; the index files stay below the same)
+DUMP_SEED = 20240  # of the board sample of an array above its share
+
+
+def sample_boards(n_boards, row_bytes, cap_bytes, seed=DUMP_SEED):
+    """The boards of an array that --dump-outputs writes: None (all of them) when
+    n_boards rows of row_bytes fit cap_bytes, else the sorted indices of as many boards
+    as fit (one at least), drawn without replacement from RandomState(seed): the same
+    boards for the same shape in every run."""
+    if n_boards * row_bytes <= cap_bytes:
+        return None
+    n = max(1, min(n_boards, cap_bytes // row_bytes))
+    return np.sort(np.random.RandomState(seed).choice(n_boards, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, eng, suffix=""):
+    """Write the engine's current step outputs (the last step's: TDEngine.step returns these
+    very buffers) as dirname/<name><suffix>.npy, float64 where the engine's array is, float32
+    otherwise (the integer arrays hold action ids, fail codes, flags and episode lengths, all
+    exact in float32).  Sampled arrays come with dirname/<name>_boards<suffix>.npy, the board
+    indices of their rows.  Returns {file name: bytes written}."""
+    os.makedirs(dirname, exist_ok=True)
+    torch.cuda.synchronize(eng.device)
+    written = {}
+    for name in OUTPUT_NAMES:
+        t = getattr(eng, name, None)
+        if t is None:
+            continue
+        kind = np.float64 if t.dtype == torch.float64 else np.float32
+        row = int(np.prod(t.shape[1:], dtype=np.int64)) * np.dtype(kind).itemsize
+        idx = sample_boards(t.shape[0], row, DUMP_OBS_BYTES if name == "obs" else DUMP_ARRAY_BYTES)
+        if idx is not None:
+            t = t[torch.from_numpy(idx).to(t.device)]
+            np.save(os.path.join(dirname, "%s_boards%s.npy" % (name, suffix)), idx.astype(np.float64))
+            written["%s_boards%s.npy" % (name, suffix)] = idx.size * 8
+        a = np.ascontiguousarray(t.cpu().numpy().astype(kind))
+        np.save(os.path.join(dirname, "%s%s.npy" % (name, suffix)), a)
+        written["%s%s.npy" % (name, suffix)] = a.nbytes
+    return written
+
+
 # --------------------------------------------------------------------------- CPU baseline
 def _cpu_worker(args):
     L, mode, multi, seconds, seed = args
@@ -394,6 +451,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own: the CPU baselines "
+                         "(C and Python restatements; --cpu-seconds, --py-cpu-seconds, --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (see docstring)")
     ap.add_argument("--workload", default="def-small", choices=sorted(WORKLOADS))
     ap.add_argument("--global-batch", type=int, default=None,
                     help="boards over all ranks, split evenly (strong scaling; default: the workload's)")
@@ -525,6 +587,8 @@ def main():
     # after timing: MAX of the clocks over ranks, and the episode statistics of the
     # timed steps gathered to rank 0 (the only exchange; RCCL on GPUs)
     guard_to = eng.guard_timeouts()
+    if args.dump_outputs:  # nothing since the last timed step has stepped a board or written a step output
+        dump_outputs(args.dump_outputs, eng, ".rank%d" % rank if world > 1 else "")
     (elapsed, avg_kernel_s, warm_step_s), per_rank, recs, clocks = collect(
         elapsed, avg_kernel_s, warm_step_s, ep_stats, ep_recs, coll, barrier_s)
     reported_world = dist.get_world_size() if world > 1 else 1  # what the process group (RCCL) reports
@@ -581,7 +645,7 @@ def main():
         }
         if exceeds:
             out["roofline"]["frac_withheld"] = why
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads, affinity, quota = baseline_threads()
             cb = cpu_baseline(L, mode, multi, args.cpu_seconds, threads, args.workload)
             cb.update(baseline_note(cb["value"], threads, affinity, quota))

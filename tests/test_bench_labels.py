@@ -174,3 +174,20 @@ def test_baseline_note_states_cores_and_projection():
     assert n["value_per_core"] == 0.5e6
     assert n["all_affinity_cores_projection"]["value"] == 128.0e6
     assert "not measured" in n["all_affinity_cores_projection"]["note"]
+
+
+def test_dump_sample_is_fixed_and_within_its_share():
+    """--dump-outputs: an array within its share is written whole; a larger one is cut to the
+    same sorted, distinct boards in every run, as many as fit its share."""
+    import numpy as np
+    assert bench.sample_boards(65536, 8, bench.DUMP_ARRAY_BYTES) is None  # reward f64 of the metric's batch
+    row = 45 * 10 * 10 * 4  # one 10x10 board's observation
+    a = bench.sample_boards(65536, row, bench.DUMP_OBS_BYTES)
+    b = bench.sample_boards(65536, row, bench.DUMP_OBS_BYTES)
+    assert np.array_equal(a, b) and a.dtype == np.int64
+    assert len(a) == bench.DUMP_OBS_BYTES // row and len(np.unique(a)) == len(a)
+    assert (np.diff(a) > 0).all() and a[0] >= 0 and a[-1] < 65536
+    assert len(bench.sample_boards(4, 3 * bench.DUMP_ARRAY_BYTES, bench.DUMP_ARRAY_BYTES)) == 1
+    # every array at its share, each with an index file of at most the same size: below 64 MB
+    n = len(bench.OUTPUT_NAMES) - 1
+    assert bench.DUMP_OBS_BYTES + 2 * n * bench.DUMP_ARRAY_BYTES + bench.DUMP_ARRAY_BYTES <= 64 * 10 ** 6
