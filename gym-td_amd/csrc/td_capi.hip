@@ -788,6 +788,41 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   return 0;
 }
 
+void td_mask_io_init(td_mask_io* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof *io);
+  io->size = (uint32_t)sizeof(td_mask_io);
+  io->abi = TD_ABI_VERSION;
+}
+
+int td_action_mask(td_handle* h, const td_mask_io* io, void* stream) {
+  if (!io) return fail("td_action_mask: NULL io");
+  // the two header words first, as td_step
+  if (io->size != (uint32_t)sizeof(td_mask_io) || io->abi != (uint32_t)TD_ABI_VERSION)
+    return fail("td_action_mask: td_mask_io has size %u / abi %u, this library expects size %u / abi %d "
+                "(call td_mask_io_init)", io->size, io->abi, (unsigned)sizeof(td_mask_io), TD_ABI_VERSION);
+  if (!h) return fail("td_action_mask: NULL handle");
+  if (!io->def_mask && !io->def_code && !io->atk_mask) return fail("td_action_mask: no output wanted (all three are NULL)");
+  const bool def_out = io->def_mask || io->def_code;
+  if (def_out && h->mode == TD_MODE_ATK) return fail("td_action_mask: TD-atk has no defender side (def_mask / def_code)");
+  if (io->atk_mask && h->mode == TD_MODE_DEF) return fail("td_action_mask: TD-def has no attacker side (atk_mask)");
+  const size_t row = (size_t)6 * h->NC + (h->multi ? 0 : 1);
+  size_t pitch = row;
+  if (def_out && io->def_pitch != 0) {
+    if (h->multi) return fail("td_action_mask: def_pitch must be 0 with multi-action (rows are [6][L][L], contiguous)");
+    if (io->def_pitch < row || io->def_pitch > kMaskMaxPitch)
+      return fail("td_action_mask: def_pitch %zu outside [%zu, %zu] (6 L^2 + 1 bytes per row at L = %d)", io->def_pitch, row,
+                  kMaskMaxPitch, h->L);
+    pitch = io->def_pitch;
+  }
+  MaskArgs a;
+  a.B = h->B; a.L = h->L; a.multi = h->multi; a.xcd_map = h->xcd_map;
+  a.hdr = h->d_hdr; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.cfg = h->d_cfg + h->epoch;
+  a.def_mask = io->def_mask; a.def_code = io->def_code; a.atk_mask = io->atk_mask; a.def_pitch = pitch;
+  HIP_OK(launch_mask(a, (hipStream_t)stream));
+  return 0;
+}
+
 int td_set_step_kernel(td_handle* h, int kind) {
   if (!h) return fail("NULL handle");
   if (kind < TD_KERNEL_AUTO || kind > TD_KERNEL_SMALL2) return fail("td_set_step_kernel: unknown kernel kind %d", kind);

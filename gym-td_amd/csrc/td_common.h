@@ -88,6 +88,9 @@ __host__ __device__ inline int en_ep(uint32_t u) { return (int)(u >> 24); }
 __host__ __device__ inline uint32_t tw_pack(int cell, int type, int lv, int ec, int eu) {
   return (uint32_t)cell | ((uint32_t)type << 12) | ((uint32_t)lv << 14) | ((uint32_t)ec << 16) | ((uint32_t)eu << 24);
 }
+__host__ __device__ inline int tw_cell(uint32_t u) { return (int)(u & 0xfffu); }
+__host__ __device__ inline int tw_type(uint32_t u) { return (int)((u >> 12) & 3u); }
+__host__ __device__ inline int tw_lv(uint32_t u) { return (int)((u >> 14) & 1u); }
 __host__ __device__ inline int tw_ec(uint32_t u) { return (int)((u >> 16) & 0xffu); }
 __host__ __device__ inline int tw_eu(uint32_t u) { return (int)(u >> 24); }
 

@@ -103,6 +103,24 @@ hipError_t launch_refill(const StepArgs& a, hipStream_t s, int guard = 0);
 // on the boards in a.reset_mask (nullptr = all).
 hipError_t launch_opponent(const StepArgs& a, int side, int level, hipStream_t s);
 
+// Legal-action masks of the boards' present state (td_action_mask; td_mask.hip): which
+// action the next step would execute.  Reads the header, the cell words (map[6] in bits
+// 24-31), the tower words and the current constant block; writes only the outputs.
+struct MaskArgs {
+  int B, L, multi;
+  int xcd_map;           // block i serves board xcd_board(i, B) (else board i), as the step
+  const TdHdr* hdr;
+  const uint32_t* tw_inf;
+  const uint32_t* cells;
+  const TdDevCfg* cfg;   // the current constant block
+  uint8_t* def_mask;     // [B][def_pitch] or nullptr
+  uint8_t* def_code;     // [B][def_pitch] or nullptr
+  uint8_t* atk_mask;     // [B][3][5] or nullptr
+  size_t def_pitch;      // bytes per board: >= 6 L^2 + 1 (discrete), 6 L^2 (multi-action)
+};
+constexpr size_t kMaskMaxPitch = 1u << 16;
+hipError_t launch_mask(const MaskArgs& a, hipStream_t s);
+
 // Staged layouts per board: sixteen episodes of slack for the side refills, and the
 // ring guard (td_refill_kernel) needs to run only every NSLOT - 1 steps.  (NSLOT = 4 with
 // a guard every 3rd step: +4 % / +7-9 % per step at 8,192 / 4,096 boards, profiles/r03/s13.)

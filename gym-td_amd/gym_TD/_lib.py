@@ -53,6 +53,17 @@ class TdStepIO(ctypes.Structure):
         super().__init__(**kw)
 
 
+class TdMaskIO(ctypes.Structure):
+    """struct td_mask_io (tdstep.h): the size / ABI header, the three device outputs, the row pitch."""
+    _fields_ = [("size", ctypes.c_uint32), ("abi", ctypes.c_uint32), ("def_mask", c_vp), ("def_code", c_vp),
+                ("atk_mask", c_vp), ("def_pitch", ctypes.c_size_t)]
+
+    def __init__(self, **kw):
+        kw.setdefault("size", ctypes.sizeof(TdMaskIO))
+        kw.setdefault("abi", ABI_VERSION)
+        super().__init__(**kw)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("libtdstep.so not found at %s -- build it with `make -C gym-td_amd/csrc` "
@@ -82,6 +93,8 @@ def _load():
         "td_last_reset_failures": (ctypes.c_int, [c_vp, c_i32p, ctypes.c_int]),
         "td_reset_layouts": (ctypes.c_int, [c_vp, c_u32p, c_i32p, ctypes.c_int, c_vp, c_vp]),
         "td_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp]),
+        "td_mask_io_init": (None, [ctypes.POINTER(TdMaskIO)]),
+        "td_action_mask": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
         "td_layout_from_roads": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_u32p]),
         "td_layout_generate": (ctypes.c_int, [c_u32p, ctypes.c_int, ctypes.c_int, c_u32p]),

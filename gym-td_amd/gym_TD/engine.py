@@ -348,6 +348,48 @@ class TDEngine(object):
         self._keep = keep  # actions stay alive until the next call
         return self.obs, self.reward, self.done
 
+    def action_mask(self, code=False):
+        """Legal-action masks of every board's present state (td_action_mask): what the next
+        step() would execute if the action were the only thing asked of that side.
+
+        Returns a dict of uint8 device tensors, by mode: ``"def"`` (B, 6 L^2 + 1), the
+        no-op last -- or (B, 6, L, L) with multi-action, each flag on its own --,
+        ``"def_code"`` (with ``code``: the fail code each operation would return, the
+        cool-down aside) and ``"atk"`` (B, 3, 5), type 4 = none.  One kernel on torch's
+        current stream, which must be the stream of step().  The tensors are the engine's
+        own buffers (allocated on first use, overwritten by the next call); the discrete
+        defender rows are padded to a multiple of 16 bytes, the returned tensor is the
+        view without the padding."""
+        B, L = self.B, self.L
+        io = getattr(self, "_mask_io", None)
+        if io is None:
+            io = self._mask_io = _lib.TdMaskIO()
+            self._mask_buf = {}
+            if self.mode != "atk":
+                if self.multi:
+                    self._mask_pitch, shape = 0, (B, 6, L, L)
+                else:
+                    self._mask_pitch = (6 * L * L + 1 + 15) & ~15
+                    shape = (B, self._mask_pitch)
+                self._mask_shape = shape
+                self._mask_buf["def"] = torch.zeros(shape, dtype=torch.uint8, device=self.device)
+                io.def_mask = self._mask_buf["def"].data_ptr()
+                io.def_pitch = self._mask_pitch
+            if self.mode != "def":
+                self._mask_buf["atk"] = torch.zeros((B, 3, 5), dtype=torch.uint8, device=self.device)
+                io.atk_mask = self._mask_buf["atk"].data_ptr()
+        if code and self.mode != "atk" and "def_code" not in self._mask_buf:
+            self._mask_buf["def_code"] = torch.zeros(self._mask_shape, dtype=torch.uint8, device=self.device)
+        io.def_code = self._mask_buf["def_code"].data_ptr() if code and self.mode != "atk" else None
+        _lib.check(_lib.lib.td_action_mask(self._h, io, self._stream()))
+        A = 6 * L * L + 1
+        out = {}
+        for k, t in self._mask_buf.items():
+            if k == "def_code" and not code:
+                continue
+            out[k] = t[:, :A] if k != "atk" and not self.multi else t
+        return out
+
     # ----------------------------------------------------------------- state
     def state_bytes(self, count):
         return _lib.lib.td_state_bytes(self._h, count)

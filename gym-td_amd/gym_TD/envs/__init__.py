@@ -172,6 +172,15 @@ class _TDBasic(object):
             self.attacker_cd, self.defender_cd = int(h["atk_cd"]), int(h["def_cd"])
         return self._obs.copy(), reward, done, (None if win < 0 else bool(win)), an
 
+    def action_mask(self):
+        """Legal actions of the present state as numpy uint8 (TDEngine.action_mask): TD-def the
+        defender's (6 L^2 + 1,) -- (6, L, L) with multi-action --, TD-atk the attacker's (3, 5),
+        TD-2p a dict of both under the action space's keys."""
+        m = {k: v[0].cpu().numpy() for k, v in self._engine.action_mask().items()}
+        if self._mode == "2p":
+            return {"Attacker": m["atk"], "Defender": m["def"]}
+        return m["def" if self._mode == "def" else "atk"]
+
     def render(self, mode="human"):
         raise NotImplementedError("rendering (TDBoard.render, pyglet) is out of scope for the device engine")
 
@@ -309,12 +318,17 @@ class TDVecEnv(object):
     episode's totals where ``done``.  ``random_agent=False`` (TDGymBasic.py:87-89,
     101-103): the built-in opponents draw from each board's layout stream, and each
     auto-reset draws the next layout right after the step that ended the episode,
-    as AsyncVectorEnv's reset() would.
+    as AsyncVectorEnv's reset() would.  ``action_mask=True``: every step() and reset() is
+    followed by the mask kernel, and ``infos['action_mask']`` (the side that acts; the
+    defender's in TD-2p) and ``infos['action_mask_attacker']`` (TD-atk, TD-2p) hold the legal actions
+    of the state the step left (TDEngine.action_mask); after reset(), ``action_masks()``.
     """
 
     def __init__(self, map_size, num_envs, mode="def", difficulty=1, multi_action=None, seed=0, global_offset=0,
-                 device=None, info=True, autoreset=True, host_io=False, random_agent=True):
+                 device=None, info=True, autoreset=True, host_io=False, random_agent=True, action_mask=False):
         self.map_size, self.num_envs, self.mode = int(map_size), int(num_envs), mode
+        self.with_action_mask = bool(action_mask)
+        self._masks = None
         seeds = np.arange(num_envs, dtype=np.int64) + int(seed) + int(global_offset)
         self.engine = TDEngine(map_size, num_envs, mode, multi_action, difficulty, device=device,
                                np_seeds=seeds, py_seeds=seeds, autoreset=autoreset, info=info, host_io=host_io,
@@ -330,7 +344,15 @@ class TDVecEnv(object):
     def reset(self, max_retries=64):
         obs, skipped = self.engine.reset_all(max_retries)  # failing draws: the reference raises / hangs
         self.roadgen_failures += skipped
+        if self.with_action_mask:
+            self._masks = self.engine.action_mask()
         return obs
+
+    def action_masks(self):
+        """The legal actions of the present state, computed now: a dict of uint8 device
+        tensors, ``"def"`` and / or ``"atk"`` as the mode has them (TDEngine.action_mask)."""
+        self._masks = self.engine.action_mask()
+        return self._masks
 
     def step(self, actions):
         if self.mode == "def":
@@ -354,6 +376,11 @@ class TDVecEnv(object):
             if e.real_atk is not None:
                 infos["RealActionAttacker"] = e.real_atk
                 infos["FailCodeAttacker"] = e.fail_atk
+        if self.with_action_mask:
+            m = self._masks = e.action_mask()
+            infos["action_mask"] = m["atk" if self.mode == "atk" else "def"]
+            if self.mode != "def":
+                infos["action_mask_attacker"] = m["atk"]
         return obs, rew, done, infos
 
     def close(self):

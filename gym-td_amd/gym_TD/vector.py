@@ -128,6 +128,12 @@ class VectorEnv(object):
                             "FailCode": fc})
         return tuple(out)
 
+    def action_masks(self):
+        """Legal actions of every env's present state, numpy uint8 copies: ``"def"``
+        (N, 6 L^2 + 1) -- (N, 6, L, L) with multi-action -- and / or ``"atk"`` (N, 3, 5), as
+        the env id has the sides (TDEngine.action_mask)."""
+        return {k: v.cpu().numpy().copy() for k, v in self.vec.action_masks().items()}
+
     def close(self):
         if not self.closed:
             self.vec.close()

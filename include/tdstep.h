@@ -197,6 +197,49 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
  * per-element one (same bytes, slower). */
 int td_step(td_handle* h, const td_step_io* io, void* stream);
 
+/* Legal-action masks: for every board and every action, whether the NEXT td_step would
+ * execute that action if it were the only thing asked of that side -- decided on the device
+ * from the board's present state with the step's own comparisons, so a policy can sample
+ * legal moves only (the reference reports legality after the fact, info['FailCode'] /
+ * ['RealAction']; its trainer's one-bit form is AllowNextMove, train/main.py:130-132).
+ * A td_set_config between the mask and the step voids the mask.
+ *   def_mask  uint8, discrete [B][def_pitch]: entry a in [0, 6 L^2], a = op * L^2 + cell
+ *             (TDDefense.py:65-67).  The no-op a = 6 L^2 is always 1; any other a is 1 iff the
+ *             defender's cool-down is <= 1 (the gate of TDDefense.py:39,64 after the decrement)
+ *             and the operation would return fail code 0.  Bytes [6 L^2 + 1, def_pitch) are
+ *             written as 0.  Multi-action: [B][6][L][L], each entry = that flag alone would
+ *             succeed (flags set together interact: out of scope).
+ *   def_code  uint8, same shape: the fail code the operation would return, the cool-down
+ *             aside, tested in the step's order -- build: 1 cost (TDBoard.py:228), 2 position
+ *             (:232), 6 the device's 32-tower capacity; level-up: 4 no tower (:269-271),
+ *             3 level (:252), 1 cost (:256, current config epoch); destruct: 4 no tower.
+ *             The no-op and the padding read 0.  def_mask == (def_code == 0 && cool-down <= 1)
+ *             except the no-op.
+ *   atk_mask  uint8 [B][3][5]: entry (road, t).  t = 4 (none) is always 1; t < 4 is 1 iff
+ *             road < num_roads, the attacker's cool-down is <= 1, fewer than 128 enemies live
+ *             and cost_atk >= enemy_cost[t][lv], lv as the header's steps give it
+ *             (steps / max_episode_steps >= enemy_upgrade_at, TDBoard.py:201).
+ *   def_pitch discrete: bytes between rows, 0 = 6 L^2 + 1, else >= 6 L^2 + 1 (and <= 65,536);
+ *             multi-action: must be 0.  Rows whose start and pitch are multiples of 16 are
+ *             stored in 16-B pieces throughout (same bytes at any alignment).
+ * A board that was never reset (its road generation failed) has only the always-legal entries.
+ * NULL = not wanted; an output for a side the mode lacks, all three NULL, a bad pitch or a
+ * size / abi mismatch (checked first, as td_step) return < 0 and launch nothing.
+ * Asynchronous on `stream`, which must be the step's stream: the kernel reads the state the
+ * last td_step (and, with random_agent = 0 and auto-reset, the reset kernel behind it, on
+ * that stream too) left, and writes nothing but these outputs. */
+typedef struct td_mask_io {
+  uint32_t size;
+  uint32_t abi;
+  uint8_t* def_mask;
+  uint8_t* def_code;
+  uint8_t* atk_mask;
+  size_t def_pitch;
+} td_mask_io;
+/* Zero *io and set its size / abi words. */
+void td_mask_io_init(td_mask_io* io);
+int td_action_mask(td_handle* h, const td_mask_io* io, void* stream);
+
 /* Which step kernel td_step launches (one wave per board in all three; they differ in
  * occupancy and load schedule, not in results):
  *   TD_KERNEL_LARGE  td_step_kernel        several rounds of waves (7 per SIMD), live slots
