@@ -20,6 +20,7 @@ import numpy as np
 # --------------------------------------------------------------------------
 
 FAIL_SUCCESS, FAIL_COST, FAIL_POS, FAIL_LVMAX, FAIL_TARGET, FAIL_CLUSTER = range(6)  # utils/fail_code.py:1-6
+FAIL_CAP = 6  # no reference counterpart: the device's answer to a build on a full tower list (gym_TD/masks.py FC_CAPACITY)
 
 
 class Config(object):
@@ -380,10 +381,19 @@ def _fire(tw, enemies, cfg):
 
 
 class Board(object):
-    """TDBoard (TDBoard.py:10-385), minus rendering."""
+    """TDBoard (TDBoard.py:10-385), minus rendering.
 
-    def __init__(self, L, num_roads, rng, cfg, hp, roads=None):
+    ``enemy_cap`` / ``tower_cap`` (default None: no cap, the reference's rules exactly)
+    restate the device's fixed list capacities (include/tdstep.h td_board_flag): a summon
+    into a full enemy list is refused like one the attacker cannot pay for, a build on a
+    full tower list fails with FAIL_CAP.  ``refused`` ([summons, builds], shared with the
+    Env so that it outlives a reset) counts those refusals: a board with a non-zero count
+    is one the device flags TD_FLAG_EN_OVERFLOW / TD_FLAG_TW_OVERFLOW."""
+
+    def __init__(self, L, num_roads, rng, cfg, hp, roads=None, enemy_cap=None, tower_cap=None, refused=None):
         self.L, self.cfg, self.hp = L, cfg, hp
+        self.enemy_cap, self.tower_cap = enemy_cap, tower_cap
+        self.refused = [0, 0] if refused is None else refused
         if roads is None:
             roads = create_road(rng, L, num_roads)
         self.roads = roads
@@ -452,6 +462,9 @@ class Board(object):
             e = Enemy(cfg, t, lv, st, int(self.map[4, st[0], st[1]]))
             if self.cost_atk < e.cost:
                 real.append(cfg.enemy_types)
+            elif self.enemy_cap is not None and len(self.enemies) >= self.enemy_cap:
+                self.refused[0] += 1  # after the cost check, free of charge (td_step.hip summon_cluster)
+                real.append(cfg.enemy_types)
             else:
                 self.cost_atk -= e.cost
                 self.enemies.append(e)
@@ -480,6 +493,10 @@ class Board(object):
             return False
         if self.map[6, loc[0], loc[1]] > 0:
             self.fail_code = FAIL_POS
+            return False
+        if self.tower_cap is not None and len(self.towers) >= self.tower_cap:
+            self.refused[1] += 1  # after the cost and position checks (td_step.hip tower_build)
+            self.fail_code = FAIL_CAP
             return False
         self.towers.append(tw)
         self.cost_def -= tw.cost
@@ -606,8 +623,10 @@ class Env(object):
     """
 
     def __init__(self, L, mode=MODE_DEF, difficulty=1, seed=0, opp_seed=None, cfg=None, hp=None,
-                 random_agent=True, road_attempts=None):
+                 random_agent=True, road_attempts=None, enemy_cap=None, tower_cap=None):
         self.L, self.mode, self.difficulty = L, mode, difficulty
+        self.enemy_cap, self.tower_cap = enemy_cap, tower_cap
+        self.refused = [0, 0]  # [summons, builds] refused by a cap since the env was made (see Board)
         self.cfg = cfg or Config()
         self.hp = hp or Hyper()
         self.random_agent = random_agent
@@ -621,7 +640,8 @@ class Env(object):
     def reset(self):
         self.num_roads = self.np_random.randint(low=1, high=self.hp.max_num_of_roads + 1)
         self._board = Board(self.L, self.num_roads, None, self.cfg, self.hp,
-                            roads=create_road(self.np_random, self.L, self.num_roads, self.road_attempts))
+                            roads=create_road(self.np_random, self.L, self.num_roads, self.road_attempts),
+                            enemy_cap=self.enemy_cap, tower_cap=self.tower_cap, refused=self.refused)
         self.attacker_cd = 0
         self.defender_cd = 0
         return self._board.get_states()

@@ -7,11 +7,16 @@ The episodes run to the 1,200-step limit (base_LP raised so leaks never end them
 every board crosses the enemy-upgrade threshold (progress >= 0.75, TDBoard.py:201),
 finishes its episode and auto-resets onto its next staged layout (failing draws
 skipped on both sides).  The two shapes are chosen so that boards carry more than
-64 live enemies (10x10, an idle defender against a fast attacker) and more than 16
-towers (20x20, a builder defender): the step kernel prefetches 16 enemy and 16 tower
-slots with the header and loads the rest afterwards (the large kernel loads exactly the
-live slots once the header is in), and lanes hold enemies l and l + 64 (td_step.hip
-prefetch_issue / load_board / board_step).  Each shape runs on all three step kernels."""
+16 live enemies (10x10, an idle defender against a fast attacker: 25-65, asserted as
+more than 48) and more than 16 towers (20x20, a builder defender): the step kernel
+prefetches 16 enemy and 16 tower slots with the header and loads the rest afterwards
+(the large kernel loads exactly the live slots once the header is in; td_step.hip
+prefetch_issue / load_board).  These runs do not pin the upper half of the enemy list
+(lanes hold enemies l and l + 64, board_step): a few boards here go just past 64 enemies
+for a while (enough to trip over a wrong compaction offset there), but nothing below
+asserts it (`max_en > 48`), let alone which of the second enemy's branches ran.
+Boards with 65-128 enemies and full tower lists are pinned in tests/test_gpu_crowded.py.
+Each shape runs on all three step kernels."""
 import copy
 
 import numpy as np
@@ -60,7 +65,8 @@ def _reset_skipping(env):
 
 
 # 10x10: an idle defender against a fast attacker (cost rates 4 -> 8 per step): 25-65 live
-# enemies per board late in the episode, past the 16 prefetched slots and past lane 63.
+# enemies per board late in the episode, past the 16 prefetched slots (lane 63 and beyond:
+# tests/test_gpu_crowded.py).
 # 20x20: a builder defender: up to ~24 towers per board.
 @pytest.mark.parametrize("kernel", ("large", "small", "small2"))
 @pytest.mark.parametrize("L,B,p_build,over", [
