@@ -88,6 +88,8 @@ __device__ __forceinline__ float bitf(uint32_t m, int ch) { return (float)((m >>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 // Channel kinds of the observation (TDBoard.get_states, :112-143).
 enum ObsKind : int { OK_BIN, OK_CONST, OK_D9, OK_ENEMY };

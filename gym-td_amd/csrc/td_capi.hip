@@ -82,7 +82,9 @@ struct td_handle {
   int L = 0, NC = 0, B = 0, mode = 0, multi = 0, difficulty = 1, device = 0, autoreset = 1;
   int opp_np = 0;  // random_agent=False
   int small = 0, obs_wt = 0;  // the step kernel (0 large, 1 small, 2 small2), write-through observation stores
-  int small_auto = 0;         // td_create's choice (TD_KERNEL_AUTO)
+  int kernel_forced = 0;      // td_set_step_kernel chose the kind (else TD_KERNEL_AUTO: auto_kernel)
+  int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
+  int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   std::string kernel_name;    // td_step_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
@@ -219,6 +221,7 @@ StepArgs base_args(td_handle* h) {
   a.opp_np = h->opp_np;
   a.small = h->small;
   a.obs_wt = h->obs_wt;
+  a.obs_f16 = h->obs_fmt == TD_OBS_F16 ? 1 : 0;
   a.hdr = h->d_hdr; a.en_lp = h->d_en_lp; a.en_mg = h->d_en_mg; a.en_inf = h->d_en_inf;
   a.tw_cd = h->d_tw_cd; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.opp_mt = h->d_opp; a.opp_hot = h->d_hot;
   a.np_mt = h->d_np; a.nxt = h->d_nxt; a.scratch = h->d_scratch; a.scratch_stride = h->scratch_stride;
@@ -250,16 +253,51 @@ void parallel_for(int n, F fn) {
 // 256-MiB Infinity Cache (scripts/storepol.hip: 21.8 vs 30.0 us at 8,192 boards).
 int apply_kernel(td_handle* h, int small) {
   h->small = small;
-  const double obs_bytes = (double)h->B * NCH * h->NC * 4.0;
+  const bool f16 = h->obs_fmt == TD_OBS_F16;
+  const double obs_bytes = (double)h->B * NCH * h->NC * (f16 ? 2.0 : 4.0);
   // (Write-through beyond the Infinity Cache -- any kernel, TD_OBS_WT=1 -- measured 1.5-1.7x
   // slower steps at 16,384-65,536 boards, profiles/r03/s21.)
   h->obs_wt = h->small && obs_bytes <= 192.0 * 1024 * 1024 ? 1 : 0;
   const bool has_small = h->L == 10 || h->L == 20 || h->L == 30;
   const char* k = !has_small || small == 0 ? "td_step_kernel" : small == 1 ? "td_step_kernel_small" : "td_step_kernel_small2";
   char buf[96];
-  std::snprintf(buf, sizeof buf, "%s<%d, %d, %s>", k, has_small ? h->L : 0, h->mode, h->multi ? "true" : "false");
+  std::snprintf(buf, sizeof buf, "%s%s<%d, %d, %s>", k, f16 ? "_f16" : "", has_small ? h->L : 0, h->mode,
+                h->multi ? "true" : "false");
   h->kernel_name = buf;
   return 0;
+}
+
+// TD_KERNEL_AUTO: the small-batch kernel where the whole batch is one round of waves,
+// two waves per board up to half a round -- and again over a few rounds, where the
+// second wave's half of the observation shortens every board's step more than the
+// halved residency costs (single-action boards, profiles/r03/s7, same box: 10x10
+// 12,288 / 16,384 boards 237.8 / 255.4 vs 224.0 / 238.5 M env-steps/s with the large
+// kernel, 32,768 a tie; 30x30 16,384 / 32,768 boards 30.8 / 31.9 vs 29.8 / 31.2 M, 65,536
+// 30.0 vs 30.2 M; TD-2p 20x20 multi-action at 16,384: 48.0 vs 51.5 M in round 3, 54.0 vs
+// 52.1 M on the round-4 build, r04/s10).
+// td_set_step_kernel overrides.
+int auto_kernel(const td_handle* h) {
+  const bool f16 = h->obs_fmt == TD_OBS_F16;
+  const int resident = h->resident[f16][0], resident2 = h->resident[f16][1];
+  // two-wave kernel up to this many rounds (TD-2p 20x20 multi-action at 16,384 boards:
+  // 303.3-303.6 vs 314-315 us per step with the large kernel, profiles/r04/s10; TD-def
+  // 10x10 at every batch above one round since round 5: 32,768 / 49,152 / 65,536 boards
+  // 107.5-107.9 / 156.5-156.8 / 203.4-204.1 vs 111.7-111.9 / 160.6-160.9 / 208.2-208.4 us,
+  // profiles/r05/s33, s34)
+  const int rounds2 = h->multi ? (h->L == 20 && h->mode == TD_MODE_2P ? 8 : 0)
+                               : h->L == 10 ? (h->mode == TD_MODE_DEF ? (1 << 20) : 3) : h->L == 30 ? 10 : 0;
+  // The float16 observation at 10x10: the one-wave small kernel at every batch above half a
+  // round.  With half the bytes to store the step is bound by the boards in flight, not by
+  // the store stream, and the second wave halves them (TD-def 12,288 / 16,384 / 32,768 /
+  // 65,536 boards: 38.9 / 47.5 / 82.7 / 158.4 us per step against 45.2 / 57.1 / 103.4 /
+  // 201.1 two-wave and 39.3 / 49.2 / 88.8 / 172.0 large; TD-atk at 16,384 and TD-2p at
+  // 32,768 alike, profiles/obs_f16/f16_sizes.jsonl).  At 20x20 and 30x30 the three kernels
+  // are within 1-3 % of each other in float16, the float32 rule's choice never the slowest.
+  if (f16 && h->L == 10) return h->B <= resident2 ? 2 : 1;
+  return h->B <= resident2                                  ? 2
+         : h->B <= resident                                 ? 1
+         : (int64_t)h->B <= (int64_t)rounds2 * resident     ? 2
+                                                            : 0;
 }
 
 // Drop staged layouts: they were drawn from a stream that has been replaced.
@@ -495,31 +533,16 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
     if (!rc && hipEventCreateWithFlags(&h->ev_step, fl) != hipSuccess) rc = fail("event");
   }
   if (rc) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
-  {  // TD_KERNEL_AUTO: the small-batch kernel where the whole batch is one round of waves,
-     // two waves per board up to half a round -- and again over a few rounds, where the
-     // second wave's half of the observation shortens every board's step more than the
-     // halved residency costs (single-action boards, profiles/r03/s7, same box: 10x10
-     // 12,288 / 16,384 boards 237.8 / 255.4 vs 224.0 / 238.5 M env-steps/s with the large
-     // kernel, 32,768 a tie; 30x30 16,384 / 32,768 boards 30.8 / 31.9 vs 29.8 / 31.2 M, 65,536
-     // 30.0 vs 30.2 M; TD-2p 20x20 multi-action at 16,384: 48.0 vs 51.5 M in round 3, 54.0 vs
-     // 52.1 M on the round-4 build, r04/s10).
-     // td_set_step_kernel overrides.
+  {  // boards resident at once, per format and kernel: what TD_KERNEL_AUTO goes by (auto_kernel)
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    const int resident = step_resident_boards(base_args(h), cus, 1);
-    const int resident2 = step_resident_boards(base_args(h), cus, 2);
-    // two-wave kernel up to this many rounds (TD-2p 20x20 multi-action at 16,384 boards:
-    // 303.3-303.6 vs 314-315 us per step with the large kernel, profiles/r04/s10; TD-def
-    // 10x10 at every batch above one round since round 5: 32,768 / 49,152 / 65,536 boards
-    // 107.5-107.9 / 156.5-156.8 / 203.4-204.1 vs 111.7-111.9 / 160.6-160.9 / 208.2-208.4 us,
-    // profiles/r05/s33, s34)
-    const int rounds2 = h->multi ? (h->L == 20 && h->mode == TD_MODE_2P ? 8 : 0)
-                                 : h->L == 10 ? (h->mode == TD_MODE_DEF ? (1 << 20) : 3) : h->L == 30 ? 10 : 0;
-    h->small_auto = n_boards <= resident2                            ? 2
-                    : n_boards <= resident                           ? 1
-                    : (int64_t)n_boards <= (int64_t)rounds2 * resident ? 2
-                                                                     : 0;
-    if (apply_kernel(h, h->small_auto)) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
+    StepArgs ra = base_args(h);
+    for (int f = 0; f < 2; ++f) {
+      ra.obs_f16 = f;
+      h->resident[f][0] = step_resident_boards(ra, cus, 1);
+      h->resident[f][1] = step_resident_boards(ra, cus, 2);
+    }
+    if (apply_kernel(h, auto_kernel(h))) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
   }
   std::vector<uint32_t> seeds(B);
   for (size_t b = 0; b < B; ++b) seeds[b] = (uint32_t)b;
@@ -829,10 +852,28 @@ int td_set_step_kernel(td_handle* h, int kind) {
   if (kind >= TD_KERNEL_SMALL && h->L != 10 && h->L != 20 && h->L != 30)
     return fail("td_set_step_kernel: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", h->L);
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
-  return apply_kernel(h, kind == TD_KERNEL_AUTO ? h->small_auto : kind - 1);
+  h->kernel_forced = kind != TD_KERNEL_AUTO;
+  return apply_kernel(h, kind == TD_KERNEL_AUTO ? auto_kernel(h) : kind - 1);
 }
 
 int td_step_kernel(td_handle* h) { return h ? h->small + 1 : fail("NULL handle"); }
+
+// The observation's element.  A kernel kind the caller forced stays, TD_KERNEL_AUTO is
+// resolved again for the new format (auto_kernel); the write-through policy and the
+// kernel's name follow the new byte size.
+int td_set_obs_format(td_handle* h, int fmt) {
+  if (!h) return fail("NULL handle");
+  if (fmt != TD_OBS_F32 && fmt != TD_OBS_F16) return fail("td_set_obs_format: unknown format %d (TD_OBS_F32 = 0, TD_OBS_F16 = 1)", fmt);
+  HIP_OK(hipDeviceSynchronize());  // launches already queued keep the format they were enqueued with
+  h->obs_fmt = fmt;
+  return apply_kernel(h, h->kernel_forced ? h->small : auto_kernel(h));
+}
+
+int td_obs_format(td_handle* h) { return h ? h->obs_fmt : fail("NULL handle"); }
+
+size_t td_obs_bytes(td_handle* h) {
+  return h ? (size_t)h->B * NCH * h->NC * (h->obs_fmt == TD_OBS_F16 ? 2u : 4u) : 0;
+}
 
 const char* td_step_kernel_name(td_handle* h) { return h ? h->kernel_name.c_str() : ""; }
 

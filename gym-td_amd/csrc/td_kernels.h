@@ -53,7 +53,7 @@ struct StepArgs {
   int epoch;
   const int64_t* def_act;
   const int64_t* atk_act;
-  float* obs;
+  float* obs;           // _Float16* with obs_f16
   double* reward;
   uint8_t* done;
   int64_t* real_def;
@@ -70,6 +70,7 @@ struct StepArgs {
   const uint8_t* reset_mask;  // reset kernel only (nullptr = all boards)
   int xcd_map;   // block i steps board xcd_board(i, B) (else board i)
   int edge_wt;   // observation lines shared with a neighbouring board: 2 plain, 1 write-through (write_obs_lines)
+  int obs_f16;   // the observation is _Float16 [B][45][L][L] (td_set_obs_format): the *_f16 step kernels
 };
 
 constexpr int NXCD = 8;  // XCDs of an MI355X: block i runs on XCD i % 8
@@ -87,8 +88,12 @@ __host__ __device__ inline int xcd_board(int i, int B) {
 
 // ev0 / ev1: optional timing events bound to the step kernel's dispatch (td_kernel_timing).
 hipError_t launch_step(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+// The step with a float16 observation (a.obs_f16; called by launch_step; td_step_f16.hip).
+hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+int step_resident_boards_f16(const StepArgs& a, int cus, int waves);
 // Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute
-// units, for the one-wave (td_step_kernel_small) or two-wave (td_step_kernel_small2) build.
+// units, for the one-wave (td_step_kernel_small) or two-wave (td_step_kernel_small2) build
+// of the observation format a.obs_f16.
 int step_resident_boards(const StepArgs& a, int cus, int waves);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),
 // drawing their layouts from the shared numpy stream now (same stream, after the step).

@@ -994,6 +994,7 @@ __device__ __forceinline__ float obs_value(const Smem<NC>& S, int ch, int cell, 
 // read back by the kernel; as plain stores the dirty lines fill the XCD L2s and
 // every state load behind them waits on a write-back (measured: 16 % slower).
 __device__ __forceinline__ void obs_store(f32x4* p, f32x4 v) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void obs_store(u32x2* p, u32x2 v) { __builtin_nontemporal_store(v, p); }
 // The two lines a board shares with its neighbours (written half by this wave, half
 // by a wave on another XCD) are stored write-through (sc1) instead: two non-temporal
 // partial writes of one line cost ~7 % of the whole stream (scripts/storepol.hip:
@@ -1001,6 +1002,43 @@ __device__ __forceinline__ void obs_store(f32x4* p, f32x4 v) { __builtin_nontemp
 __device__ __forceinline__ void obs_store_shared(__amdgpu_buffer_rsrc_t r, int off, f32x4 v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, 16);  // aux 16 = sc1
 }
+__device__ __forceinline__ void obs_store_shared(__amdgpu_buffer_rsrc_t r, int off, u32x2 v) {
+  __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, 16);
+}
+
+// Buffer store of one unit; AUX: 0 plain, 2 non-temporal, 16 write-through (sc1).  A lane
+// whose offset lies beyond the resource's range is dropped by the hardware.
+template <int AUX>
+__device__ __forceinline__ void obs_buf_store(f32x4 v, __amdgpu_buffer_rsrc_t r, uint32_t off) {
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), r, off, 0, AUX);
+}
+template <int AUX>
+__device__ __forceinline__ void obs_buf_store(u32x2 v, __amdgpu_buffer_rsrc_t r, uint32_t off) {
+  __builtin_amdgcn_raw_buffer_store_b64(v, r, off, 0, AUX);
+}
+
+// The observation's output element (td_set_obs_format): float, or _Float16 -- the same
+// float32 value, rounded to nearest-even by the last conversion (the _Float16 cast:
+// v_cvt_f16_f32 or gfx950's v_cvt_pk_f16_f32, both under the default rounding mode; never
+// v_cvt_pkrtz_f16_f32, which rounds toward zero).  One unit
+// of the writers below is a quad of 4 cells of one plane in either format: 16 B of
+// float32, 8 B of float16, so a 128-B line holds 8 or 16 units.
+template <class OT>
+struct ObsFmt;
+template <>
+struct ObsFmt<float> {
+  typedef f32x4 Unit;
+  static constexpr int UB = 16, UPL = 8;  // bytes per unit, units per 128-B line
+  static __device__ __forceinline__ Unit pack(float a, float b, float c, float d) { return f32x4{a, b, c, d}; }
+};
+template <>
+struct ObsFmt<_Float16> {
+  typedef u32x2 Unit;
+  static constexpr int UB = 8, UPL = 16;
+  static __device__ __forceinline__ Unit pack(float a, float b, float c, float d) {
+    return __builtin_bit_cast(u32x2, f16x4{(_Float16)a, (_Float16)b, (_Float16)c, (_Float16)d});
+  }
+};
 
 // The (45, L, L) float32 observation of one board.  The wave writes the batch's
 // observation stream in 128-B-aligned 1-KB windows: store k covers the 16-B units
@@ -1012,33 +1050,36 @@ __device__ __forceinline__ void obs_store_shared(__amdgpu_buffer_rsrc_t r, int o
 // (scripts/membench.hip: 4.3 vs 5.0-5.1 TB/s), so the channel-major walk of the
 // planes (800-B runs per store) is not line-aligned enough.  Lane unit i of the board
 // is channel i / Q, quad i % Q (Q = L*L/4 quads of 4 cells per plane).
-template <int NC, int LT>
-__device__ __forceinline__ void write_obs(const Smem<NC>& S, const Ctx& x, float* out, bool any_enemy) {
+template <int NC, int LT, class OT = float>
+__device__ __forceinline__ void write_obs(const Smem<NC>& S, const Ctx& x, OT* out, bool any_enemy) {
+  typedef ObsFmt<OT> F;
+  typedef typename F::Unit Unit;
+  constexpr int UB = F::UB, UPL = F::UPL;
   const int ncr = LT ? LT * LT : x.NCr;
-  if ((ncr & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {  // else: caller buffer not 16-B aligned
+  if ((ncr & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & (UB - 1)) == 0) {  // else: caller buffer not unit-aligned
     const int Q = ncr / 4, n4 = NCH * Q;
-    f32x4* o4 = reinterpret_cast<f32x4*>(out);
-    const int mis = (int)((reinterpret_cast<uintptr_t>(o4) >> 4) & 7u);  // units of the line before the board
+    Unit* o4 = reinterpret_cast<Unit*>(out);
+    const int mis = (int)((reinterpret_cast<uintptr_t>(o4) / UB) & (UPL - 1));  // units of the line before the board
     // units [0, head) and [tail, n4) lie in lines shared with the neighbouring boards
-    const int head = mis ? 8 - mis : 0, tail = ((n4 + mis) & ~7) - mis;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o4, 0, n4 * 16, 0x00020000);
+    const int head = mis ? UPL - mis : 0, tail = ((n4 + mis) & ~(UPL - 1)) - mis;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o4, 0, n4 * UB, 0x00020000);
     const uint4* cell4 = reinterpret_cast<const uint4*>(S.cell);
     for (int i = x.lane - mis; i < n4; i += 64) {
       if (i < 0) continue;
       const int ch = i / Q, q = i - ch * Q;
       const int kind = obs_kind(ch);
-      f32x4 v;
+      Unit v;
       if (kind == OK_BIN) {
         const uint4 w = cell4[q];
         const uint32_t c = (uint32_t)ch;
-        v = f32x4{(float)((w.x >> c) & 1u), (float)((w.y >> c) & 1u), (float)((w.z >> c) & 1u),
-                  (float)((w.w >> c) & 1u)};
+        v = F::pack((float)((w.x >> c) & 1u), (float)((w.y >> c) & 1u), (float)((w.z >> c) & 1u),
+                    (float)((w.w >> c) & 1u));
       } else if (kind == OK_CONST) {
         const float c = S.chv[ch];
-        v = f32x4{c, c, c, c};
+        v = F::pack(c, c, c, c);
       } else if (kind == OK_D9) {
         const uint4 w = cell4[q];
-        v = f32x4{S.d9[w.x >> 24], S.d9[w.y >> 24], S.d9[w.z >> 24], S.d9[w.w >> 24]};
+        v = F::pack(S.d9[w.x >> 24], S.d9[w.y >> 24], S.d9[w.z >> 24], S.d9[w.w >> 24]);
       } else if (any_enemy) {  // wave-uniform
         const int e = ch - 25, st = e >> 2, t = e & 3;
         const uint32_t g4 = *reinterpret_cast<const uint32_t*>(&S.grp[t][4 * q]);
@@ -1046,18 +1087,18 @@ __device__ __forceinline__ void write_obs(const Smem<NC>& S, const Ctx& x, float
         // branch-free: read a clamped slot, keep it only where the cell has a group
         const float f0 = S.gst[g0 & (ECAP - 1)][st], f1 = S.gst[g1 & (ECAP - 1)][st];
         const float f2 = S.gst[g2 & (ECAP - 1)][st], f3 = S.gst[g3 & (ECAP - 1)][st];
-        v = f32x4{g0 != 0xffu ? f0 : 0.0f, g1 != 0xffu ? f1 : 0.0f, g2 != 0xffu ? f2 : 0.0f, g3 != 0xffu ? f3 : 0.0f};
+        v = F::pack(g0 != 0xffu ? f0 : 0.0f, g1 != 0xffu ? f1 : 0.0f, g2 != 0xffu ? f2 : 0.0f, g3 != 0xffu ? f3 : 0.0f);
       } else {
-        v = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        v = F::pack(0.0f, 0.0f, 0.0f, 0.0f);
       }
-      if (i < head || i >= tail) obs_store_shared(rs, i * 16, v);
+      if (i < head || i >= tail) obs_store_shared(rs, i * UB, v);
       else obs_store(o4 + i, v);
     }
   } else {
     const int nf = NCH * ncr;
     for (int f = x.lane; f < nf; f += 64) {
       const int ch = f / ncr;
-      out[f] = obs_value(S, ch, f - ch * ncr, any_enemy);
+      out[f] = (OT)obs_value(S, ch, f - ch * ncr, any_enemy);
     }
   }
 }
@@ -1068,12 +1109,13 @@ __device__ __forceinline__ void write_obs(const Smem<NC>& S, const Ctx& x, float
 // edge test in ~20 SALU per window): bits 0-1 the channel class (0 binary planes only,
 // 1 broadcast channels only, 2 enemy planes only, 3 mixed), bit 2 the window holds a
 // line shared with a neighbouring board.
-template <int LT>
+// UPL: units per 128-B line, 8 of float32 or 16 of float16 (ObsFmt) -- so many misalignments.
+template <int LT, int UPL = 8>
 struct ObsWinTab {
-  static constexpr int Q = LT * LT / 4, N4 = NCH * Q, K = (N4 + 7 + 63) / 64, W = (K + 7) / 8;
-  struct T { uint32_t w[8][W]; };
+  static constexpr int Q = LT * LT / 4, N4 = NCH * Q, K = (N4 + UPL - 1 + 63) / 64, W = (K + 7) / 8;
+  struct T { uint32_t w[UPL][W]; };
   static constexpr uint32_t cls(int mis, int k) {
-    const int head = mis ? 8 - mis : 0, tail = ((N4 + mis) & ~7) - mis;
+    const int head = mis ? UPL - mis : 0, tail = ((N4 + mis) & ~(UPL - 1)) - mis;
     const int ulo = 64 * k - mis, uhi = ulo + 63;
     const int clo = (ulo < 0 ? 0 : ulo) / Q, chi = (uhi > N4 - 1 ? N4 - 1 : uhi) / Q;
     uint64_t chm = 0;
@@ -1084,7 +1126,7 @@ struct ObsWinTab {
   }
   static constexpr T make() {
     T t{};
-    for (int m = 0; m < 8; ++m)
+    for (int m = 0; m < UPL; ++m)
       for (int k = 0; k < K; ++k) t.w[m][k / 8] |= cls(m, k) << (4 * (k % 8));
     return t;
   }
@@ -1115,12 +1157,18 @@ struct ObsWinTab {
 // (a pair split across two XCDs is written back byte-masked by both L2s); 1: write-through
 // (sc1).  2 vs 1 at 65,536 boards: 1.088x vs 1.093x the algorithmic bytes, step time +-0
 // (profiles/r04/s20); non-temporal partial lines measured 233 vs 212 us (r04/s4).
-template <int NC, int LT, int KB = 0, int KE = -1, int G = 4, int PASS = 0>
-__device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, float* out, bool any_enemy, bool wt,
+//
+// OT = _Float16: the same units, windows and classes with 8-B units -- a wave store is
+// 512 B, four whole lines; a board starts at one of 16 unit offsets in its line
+// (ObsWinTab<LT, 16>) and has one window more where N4 + 15 crosses a multiple of 64.
+template <int NC, int LT, int KB = 0, int KE = -1, int G = 4, int PASS = 0, class OT = float>
+__device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, OT* out, bool any_enemy, bool wt,
                                                 int edge_wt = 1) {
   static_assert(LT >= 8, "a 128-B line spans at most two channel planes");
+  typedef ObsFmt<OT> F;
+  constexpr int UB = F::UB, UPL = F::UPL;
   constexpr int Q = LT * LT / 4, N4 = NCH * Q;
-  constexpr int K = KE >= 0 ? KE : (N4 + 7 + 63) / 64;  // windows [KB, K) of the board's (N4 + 7 + 63) / 64
+  constexpr int K = KE >= 0 ? KE : (N4 + UPL - 1 + 63) / 64;  // windows [KB, K) of the board's (N4 + UPL - 1 + 63) / 64
   constexpr uint32_t OOB = 0x80000000u;  // beyond the buffer's num_records: store dropped
   const char* const sb = reinterpret_cast<const char*>(&S);
   const int o_cell = (int)(reinterpret_cast<const char*>(S.cell) - sb);  // packed cell words (pack_obs_cells)
@@ -1128,13 +1176,13 @@ __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, flo
   const int o_chv = (int)(reinterpret_cast<const char*>(S.chv) - sb);
   const int o_d9 = (int)(reinterpret_cast<const char*>(S.d9) - sb);
   const int o_gst = (int)(reinterpret_cast<const char*>(&S.gst[0][0]) - sb);
-  const int mis = (int)((reinterpret_cast<uintptr_t>(out) >> 4) & 7u);  // units of the line before the board
-  const int head = mis ? 8 - mis : 0, tail = ((N4 + mis) & ~7) - mis;   // [0, head), [tail, N4): shared lines
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, N4 * 16, 0x00020000);
+  const int mis = (int)((reinterpret_cast<uintptr_t>(out) / UB) & (UPL - 1));  // units of the line before the board
+  const int head = mis ? UPL - mis : 0, tail = ((N4 + mis) & ~(UPL - 1)) - mis;  // [0, head), [tail, N4): shared lines
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(out, 0, N4 * UB, 0x00020000);
   const int i0 = lane - mis;
   typedef Div24<Q, N4 + 64> DivQ;  // unit -> channel (every unit read is in [0, N4))
   // the window's channel class and edge bit (wave-uniform, ObsWinTab)
-  auto wclass = [&](int k) { return (ObsWinTab<LT>::tab.w[mis][k >> 3] >> (4 * (k & 7))) & 7u; };
+  auto wclass = [&](int k) { return (ObsWinTab<LT, UPL>::tab.w[mis][k >> 3] >> (4 * (k & 7))) & 7u; };
   // only a window at either end of the board holds lanes outside it (i < 0, i >= N4):
   // clamp there, so every lane reads LDS inside the board image
   auto unit = [&](int i, uint32_t wc) { return (wc & 4u) ? (i < 0 ? 0 : (i > N4 - 1 ? N4 - 1 : i)) : i; };
@@ -1209,19 +1257,19 @@ __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, flo
           for (int c = 0; c < 4; ++c) v[c] = cv;
         }
       }
-      const f32x4 val = f32x4{v[0], v[1], v[2], v[3]};
-      const uint32_t off = (uint32_t)i * 16u;  // i < 0 or i >= N4: out of range already
+      const auto val = F::pack(v[0], v[1], v[2], v[3]);
+      const uint32_t off = (uint32_t)i * (uint32_t)UB;  // i < 0 or i >= N4: out of range already
       if (wt) {  // wave-uniform
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), rs, off, 0, 16 /* sc1 */);
+        obs_buf_store<16 /* sc1 */>(val, rs, off);
       } else if (!edge) {  // whole lines of this board only
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), rs, off, 0, 2 /* nt */);
+        obs_buf_store<2 /* nt */>(val, rs, off);
       } else {
         const bool shared = i < head || i >= tail;  // a line shared with a neighbouring board
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), rs, shared ? OOB : off, 0, 2 /* nt */);
+        obs_buf_store<2 /* nt */>(val, rs, shared ? OOB : off);
         if (edge_wt == 2)
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), rs, shared ? off : OOB, 0, 0 /* plain */);
+          obs_buf_store<0 /* plain */>(val, rs, shared ? off : OOB);
         else
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, val), rs, shared ? off : OOB, 0, 16 /* sc1 */);
+          obs_buf_store<16 /* sc1 */>(val, rs, shared ? off : OOB);
       }
     }
   }
@@ -1631,15 +1679,16 @@ __host__ __device__ constexpr int obs_half() { return ((NCH * LT * LT / 4 + 7 + 
 // After the second wave's early pass over the binary-plane windows: the first window of
 // the second wave's share of the rest, so both waves write half of the remaining
 // windows (counted at a line-aligned board; ObsWinTab class != 0).
-template <int LT>
+template <int LT, class OT = float>
 constexpr int obs_late_half() {
-  constexpr int K = (NCH * LT * LT / 4 + 7 + 63) / 64;
+  typedef ObsWinTab<LT, ObsFmt<OT>::UPL> Tab;
+  constexpr int K = Tab::K;
   int late = 0;
-  for (int k = 0; k < K; ++k) late += (ObsWinTab<LT>::cls(0, k) & 3u) != 0u;
+  for (int k = 0; k < K; ++k) late += (Tab::cls(0, k) & 3u) != 0u;
   int seen = 0;
   for (int k = 0; k < K; ++k) {
     if (2 * seen >= late) return k;
-    seen += (ObsWinTab<LT>::cls(0, k) & 3u) != 0u;
+    seen += (Tab::cls(0, k) & 3u) != 0u;
   }
   return K;
 }
@@ -1647,7 +1696,7 @@ constexpr int obs_late_half() {
 // SPLIT: the board's workgroup has a second wave (td_step_kernel_small2) that waits at
 // the one workgroup barrier of this path and then writes the second half of the
 // observation windows.
-template <int NC, int LT, int MODE, bool SCAN, bool SMALL, bool SPLIT = false>
+template <int NC, int LT, int MODE, bool SCAN, bool SMALL, bool SPLIT = false, class OT = float>
 __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const StepArgs& a, int b, const Prefetch& P,
                                            StepOut* so = nullptr) {
   const TdDevCfg& C = x.C;
@@ -1679,8 +1728,8 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
   if (u.num_roads < 1 || u.num_roads > 3) {
     // never reset (its road generation failed): nothing to step
     const int nf = NCH * x.NCr;
-    float* o = a.obs + (size_t)b * nf;
-    for (int i = x.lane; i < nf; i += 64) o[i] = 0.0f;
+    OT* o = reinterpret_cast<OT*>(a.obs) + (size_t)b * nf;
+    for (int i = x.lane; i < nf; i += 64) o[i] = (OT)0.0f;
     if (x.lane == 0) {  // every output defined: done, no reward, no action taken
       a.hdr[b].flags = u.flags | FLAG_NO_LAYOUT;
       a.reward[b] = 0.0;
@@ -1706,7 +1755,7 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     }
     return;
   }
-  float* const obs = a.obs + (size_t)b * NCH * x.NCr;
+  OT* const obs = reinterpret_cast<OT*>(a.obs) + (size_t)b * NCH * x.NCr;
   const bool wt = a.obs_wt != 0;
 
   u.atk_cd = u.atk_cd - 1 > 0 ? u.atk_cd - 1 : 0;
@@ -1853,8 +1902,8 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     enemy_stats(S, u, x);  // no-op for a board without enemies (e.g. just reset)
     channel_scalars(S, u, x);
     __syncthreads();
-    if (was_reset) write_obs_lines<NC, LT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
-    else write_obs_lines<NC, LT, 0, obs_late_half<LT>(), 4, 2>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+    if (was_reset) write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+    else write_obs_lines<NC, LT, 0, obs_late_half<LT, OT>(), 4, 2, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
   } else {
     enemy_stats(S, u, x);  // no-op for a board without enemies (e.g. just reset)
     channel_scalars(S, u, x);
@@ -1866,13 +1915,13 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     store_outputs(a, b, reward, ep_ret, real_def, ep_steps, fail_def, done, win, allow, cool, x.lane);
     // the observation last: nothing of the step is live any more, the writer has the registers
     if constexpr (LT != 0) {
-      if ((reinterpret_cast<uintptr_t>(a.obs) & 15u) == 0) {
-        write_obs_lines<NC, LT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+      if ((reinterpret_cast<uintptr_t>(a.obs) & (ObsFmt<OT>::UB - 1)) == 0) {
+        write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
       } else {
-        write_obs<NC, LT>(S, x, obs, u.n > 0);
+        write_obs<NC, LT, OT>(S, x, obs, u.n > 0);
       }
     } else {
-      write_obs<NC, LT>(S, x, obs, u.n > 0);
+      write_obs<NC, LT, OT>(S, x, obs, u.n > 0);
     }
   }
 }
@@ -1888,7 +1937,7 @@ __device__ __forceinline__ void prologue_args(const StepArgs& a) {
                "s"(a.en_inf), "s"(a.tw_cd), "s"(a.tw_inf), "s"(a.cells), "s"(a.opp_hot), "s"(a.def_act));
 }
 
-template <int LT, int MODE, bool SCAN, bool SMALL>
+template <int LT, int MODE, bool SCAN, bool SMALL, class OT = float>
 __device__ __forceinline__ void step_kernel_body(const StepArgs& a) {
   constexpr int NC = LT ? LT * LT : MAX_KERNEL_L * MAX_KERNEL_L;
   __shared__ Smem<NC> S;
@@ -1904,7 +1953,7 @@ __device__ __forceinline__ void step_kernel_body(const StepArgs& a) {
   prefetch_issue<PF, PF>(P, a, b, x.lane, x.NCr, MODE != MODE_ATK && !a.multi);
   store_cfg(S, cfgv, x.lane);  // (its load issued first: this wait leaves the board's loads in flight)
   wsync();  // every lane reads the block: no LDS access may move above its store
-  step_board<NC, LT, MODE, SCAN, SMALL>(S, x, a, b, P);
+  step_board<NC, LT, MODE, SCAN, SMALL, false, OT>(S, x, a, b, P);
 }
 
 // Large batches (several rounds of waves, HBM-write bound): 6 waves per SIMD at
@@ -1912,6 +1961,12 @@ __device__ __forceinline__ void step_kernel_body(const StepArgs& a) {
 template <int LT, int MODE, bool SCAN>
 __global__ __launch_bounds__(64) void td_step_kernel(StepArgs a) {
   step_kernel_body<LT, MODE, SCAN, false>(a);  // by value (see kargs)
+}
+// The float16 observation (td_set_obs_format): the same step, the writers instantiated
+// for _Float16.  Kernels of their own name, so the float32 kernels keep theirs.
+template <int LT, int MODE, bool SCAN>
+__global__ __launch_bounds__(64) void td_step_kernel_f16(StepArgs a) {
+  step_kernel_body<LT, MODE, SCAN, false, _Float16>(a);
 }
 
 // Batches that fit one round of waves.  8 waves per SIMD where LDS allows it (L = 10:
@@ -1921,70 +1976,37 @@ __global__ __launch_bounds__(64) void td_step_kernel(StepArgs a) {
 // 65,536 boards the same build is 7 % slower (SGPR spill code), hence two kernels.
 // The two-wave 20x20 TD-atk kernel does not fit 64 VGPRs: at 8 waves per SIMD it spilled
 // (8 B of scratch per lane), so 6.  (The multi-action scan kernels ran at 5 until the
-// flag fold's loop was kept rolled, scan_fold.)
-template <int LT, int MODE, bool SCAN>
-constexpr int small2_cap() { return LT == 20 && MODE == MODE_ATK && !SCAN ? 6 : 8; }
+// flag fold's loop was kept rolled, scan_fold.)  Nor does any two-wave 20x20 kernel with the
+// float16 observation (61-64 VGPRs in float32, 20 B of scratch per lane in float16 at 8): 6.
+template <int LT, int MODE, bool SCAN, class OT = float>
+constexpr int small2_cap() { return LT == 20 && ((MODE == MODE_ATK && !SCAN) || sizeof(OT) == 2) ? 6 : 8; }
 #define TD_SMALL_ATTR __attribute__((amdgpu_waves_per_eu(8, 8)))
-#define TD_SMALL2_ATTR __attribute__((amdgpu_waves_per_eu(small2_cap<LT, MODE, SCAN>(), small2_cap<LT, MODE, SCAN>())))
+// (TD_SMALL2_OT: the output element of the kernel being stamped out, td_step_small2.inc)
+#define TD_SMALL2_ATTR \
+  __attribute__((amdgpu_waves_per_eu(small2_cap<LT, MODE, SCAN, TD_SMALL2_OT>(), small2_cap<LT, MODE, SCAN, TD_SMALL2_OT>())))
 template <int LT, int MODE, bool SCAN>
 __global__ __launch_bounds__(64) TD_SMALL_ATTR void td_step_kernel_small(StepArgs a) {
   step_kernel_body<LT, MODE, SCAN, true>(kargs(a));
+}
+template <int LT, int MODE, bool SCAN>
+__global__ __launch_bounds__(64) TD_SMALL_ATTR void td_step_kernel_small_f16(StepArgs a) {
+  step_kernel_body<LT, MODE, SCAN, true, _Float16>(kargs(a));
 }
 
 // Batches up to half the resident waves: two waves per board.  The first steps the board
 // as in td_step_kernel_small; the second waits at one barrier and writes the second half
 // of the observation windows beside it, which shortens a board's critical path where the
 // batch leaves issue slots free (4,096 boards: 8,192 waves, 8 per SIMD).
-template <int LT, int MODE, bool SCAN>
-__global__ __launch_bounds__(128) TD_SMALL2_ATTR void td_step_kernel_small2(StepArgs a_) {
-  const StepArgs& a = kargs(a_);
-  constexpr int NC = LT * LT;
-  __shared__ Smem<NC> S;
-  __shared__ StepOut SO;
-  prologue_args(a);
-  if ((int)blockIdx.x >= a.B) return;
-  const int b = a.xcd_map ? xcd_board((int)blockIdx.x, a.B) : (int)blockIdx.x;
-  const int lane = (int)threadIdx.x & 63;
-  if (threadIdx.x < 64) {
-    const Ctx x{S.cfg, LT, NC, lane, a.cfgs, a.epoch};
-    const uint4 cfgv = load_cfg(a.cfg, lane);
-    Prefetch P;
-    prefetch_issue<PF_SMALL, PF_SMALL>(P, a, b, lane, NC, MODE != MODE_ATK && !a.multi);
-    store_cfg(S, cfgv, lane);  // (see load_cfg)
-    wsync();  // every lane reads the block: no LDS access may move above its store
-    step_board<NC, LT, MODE, SCAN, true, true>(S, x, a, b, P, &SO);
-  } else {
-    float* const obs = a.obs + (size_t)b * NCH * NC;
-    constexpr bool SCAN2 = SCAN;
-    if constexpr (SCAN2) {  // the multi-action flags, folded while the first wave loads the board
-      const bool bad = scan_fold(S, lane, NC, a.def_act + (size_t)b * 6 * NC);
-      if (lane == 0) SO.scan_bad = bad ? 1u : 0u;
-      __syncthreads();  // (A0)
-    }
-    __syncthreads();  // (A) actions and towers final, cells packed
-    if constexpr (SCAN2) {  // the real actions, beside the step (grp[1] is not touched before (B))
-      if (S.early_go && a.real_def) scan_write_real(S, lane, NC, a.real_def + (size_t)b * 6 * NC);
-    }
-    if (S.early_go) {
-      write_obs_lines<NC, LT, 0, -1, 4, 1>(S, lane, obs, false, a.obs_wt != 0, a.edge_wt);
-      // landed before (B): after an auto-reset the first wave rewrites these windows
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __syncthreads();  // (B) the board after the step and its outputs are in SO
-    const uint32_t go = SO.go;
-    if (go) {
-      static_assert(sizeof(TdHdr) == 6 * 16 && offsetof(StepOut, hdr) == 0 && alignof(StepOut) >= 16,
-                    "header copied as 6 x 16-B LDS reads");
-      if (lane < (SO.hdr_hi ? 6 : 3)) reinterpret_cast<uint4*>(a.hdr + b)[lane] = reinterpret_cast<const uint4*>(&SO.hdr)[lane];
-      store_towers(S, SO.nt, SO.tw_dirty != 0, lane, a, b);
-      store_outputs(a, b, SO, lane);
-    }
-    __syncthreads();  // (C) statistics and broadcast channels in LDS
-    if (go == 1u)
-      write_obs_lines<NC, LT, obs_late_half<LT>(), -1, 4, 2>(S, lane, obs, SO.any != 0u, a.obs_wt != 0,
-                                                            a.edge_wt);
-  }
-}
+#define TD_SMALL2_NAME td_step_kernel_small2
+#define TD_SMALL2_OT float
+#include "td_step_small2.inc"
+#undef TD_SMALL2_NAME
+#undef TD_SMALL2_OT
+#define TD_SMALL2_NAME td_step_kernel_small2_f16
+#define TD_SMALL2_OT _Float16
+#include "td_step_small2.inc"
+#undef TD_SMALL2_NAME
+#undef TD_SMALL2_OT
 
 // The built-in opponents called on their own, between steps (TDGymBasic.py:81-292,
 // called directly by demo.py:78-79): random_enemy_lv{0,1} (side 0) or
@@ -2028,6 +2050,7 @@ __global__ __launch_bounds__(64) void td_opponent_kernel(StepArgs a, int side, i
   if (x.lane < HOT_CACHE) hot[4 + x.lane] = R.cache;
 }
 
+#ifndef TD_STEP_F16_UNIT  // (the float16 unit holds the float16 step kernels alone, see launch_step_f16)
 template <int LT>
 static hipError_t launch_opponent2(const StepArgs& a, int side, int level, hipStream_t s) {
   hipLaunchKernelGGL(td_opponent_kernel<LT>, dim3(a.B), dim3(64), 0, s, a, side, level);
@@ -2042,6 +2065,7 @@ hipError_t launch_opponent(const StepArgs& a, int side, int level, hipStream_t s
     default: return launch_opponent2<0>(a, side, level, s);
   }
 }
+#endif
 
 // Layout draws are resumable (RoadGen::draw): a refill gives each board a budget of
 // walks per launch, and a draw that runs out (in practice one the reference never
@@ -2126,6 +2150,19 @@ __device__ int wave_layout(LayoutSmem<NC>& G, const StepArgs& a, int b, int retr
 // road status (the reference raises); else the board is reset, its first observation
 // written, and ROAD_OK returned.  keep_flags: an auto-reset keeps the board's flags,
 // an explicit reset clears them.
+// The first observation of a board just reset (no enemies yet).
+template <int NC, int LT, class OT>
+__device__ __forceinline__ void reset_obs(const Smem<NC>& S, const Ctx& x, const StepArgs& a, int b) {
+  OT* const o = reinterpret_cast<OT*>(a.obs) + (size_t)b * NCH * x.NCr;
+  if constexpr (LT != 0) {
+    if ((reinterpret_cast<uintptr_t>(a.obs) & (ObsFmt<OT>::UB - 1)) == 0)
+      write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, o, false, false);
+    else write_obs<NC, LT, OT>(S, x, o, false);
+  } else {
+    write_obs<NC, LT, OT>(S, x, o, false);
+  }
+}
+
 template <int NC, int LT>
 __device__ int reset_one(Smem<NC>& S, LayoutSmem<NC>& gen, const StepArgs& a, int b, int retries, bool keep_flags) {
   const int L = LT ? LT : a.L;
@@ -2158,14 +2195,9 @@ __device__ int reset_one(Smem<NC>& S, LayoutSmem<NC>& gen, const StepArgs& a, in
   channel_scalars(S, u, x);
   store_cells(S, u, x, a, b);
   pack_obs_cells(S, x);
-  if (a.obs) {
-    float* const o = a.obs + (size_t)b * NCH * x.NCr;
-    if constexpr (LT != 0) {
-      if ((reinterpret_cast<uintptr_t>(a.obs) & 15u) == 0) write_obs_lines<NC, LT>(S, x.lane, o, false, false);
-      else write_obs<NC, LT>(S, x, o, false);
-    } else {
-      write_obs<NC, LT>(S, x, o, false);
-    }
+  if (a.obs) {  // (the format a run-time branch here: a reset is no hot path, and its kernels keep one build)
+    if (a.obs_f16) reset_obs<NC, LT, _Float16>(S, x, a, b);
+    else reset_obs<NC, LT, float>(S, x, a, b);
   }
   store_board(S, u, x, a, b);
   if (x.lane == 0 && from_ring) a.lay_head[b] = head + 1u;
@@ -2315,8 +2347,6 @@ __global__ __launch_bounds__(64) void td_refill_kernel(StepArgs a, int guard) {
 // ev0 / ev1 (optional): timing events bound to the step kernel's own dispatch
 // (hipExtLaunchKernelGGL), so their interval is the kernel's start-to-end as the
 // dispatch packet timestamps it -- no marker packets around the launch.
-template <int LT>
-static hipError_t launch2(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0, hipEvent_t ev1) {
 #define TD_LAUNCH(k)                                                                    \
   do {                                                                                  \
     if (ev0) hipExtLaunchKernelGGL(k, dim3(a.B), dim3(64), 0, s, ev0, ev1, 0, a);       \
@@ -2327,6 +2357,58 @@ static hipError_t launch2(const StepArgs& a, hipStream_t s, bool reset, hipEvent
     if (ev0) hipExtLaunchKernelGGL(k, dim3(a.B), dim3(128), 0, s, ev0, ev1, 0, a);       \
     else hipLaunchKernelGGL(k, dim3(a.B), dim3(128), 0, s, a);                           \
   } while (0)
+
+#ifdef TD_STEP_F16_UNIT
+// The float16 step kernels are compiled in a unit of their own (td_step_f16.hip, which is
+// this file with TD_STEP_F16_UNIT defined): beside the float32 ones, not behind them, so
+// the library builds in the time it took before.  Kernel templates are instantiated where
+// they are launched, so this unit holds exactly the kernels named here.
+template <int LT>
+static hipError_t launch_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  const bool aligned = (reinterpret_cast<uintptr_t>(a.obs) & 7u) == 0;  // else the large kernel's per-element path
+  if constexpr (LT != 0) {
+    if (a.small == 2 && aligned) TD_STEP_DISPATCH(td_step_kernel_small2_f16, LT, a, TD_LAUNCH2);
+    else if (a.small && aligned) TD_STEP_DISPATCH(td_step_kernel_small_f16, LT, a, TD_LAUNCH);
+    else TD_STEP_DISPATCH(td_step_kernel_f16, LT, a, TD_LAUNCH);
+  } else {
+    TD_STEP_DISPATCH(td_step_kernel_f16, LT, a, TD_LAUNCH);
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  switch (a.L) {
+    case 10: return launch_f16<10>(a, s, ev0, ev1);
+    case 20: return launch_f16<20>(a, s, ev0, ev1);
+    case 30: return launch_f16<30>(a, s, ev0, ev1);
+    default: return launch_f16<0>(a, s, ev0, ev1);
+  }
+}
+
+template <int LT>
+static int resident_f16(const StepArgs& a, int cus, int waves) {
+  int n = 0;
+  hipError_t e = hipErrorInvalidValue;
+#define TD_OCC(k) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 64, 0)
+#define TD_OCC2(k) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, 128, 0)
+  if (waves == 2) TD_STEP_DISPATCH(td_step_kernel_small2_f16, LT, a, TD_OCC2);
+  else TD_STEP_DISPATCH(td_step_kernel_small_f16, LT, a, TD_OCC);
+#undef TD_OCC
+#undef TD_OCC2
+  return e == hipSuccess ? n * cus : 0;
+}
+
+int step_resident_boards_f16(const StepArgs& a, int cus, int waves) {
+  switch (a.L) {
+    case 10: return resident_f16<10>(a, cus, waves);
+    case 20: return resident_f16<20>(a, cus, waves);
+    case 30: return resident_f16<30>(a, cus, waves);
+    default: return 0;
+  }
+}
+#else
+template <int LT>
+static hipError_t launch2(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0, hipEvent_t ev1) {
   const bool aligned = (reinterpret_cast<uintptr_t>(a.obs) & 15u) == 0;
   if (reset) {
     hipLaunchKernelGGL(td_reset_kernel<LT>, dim3(a.B), dim3(64), 0, s, a);
@@ -2337,8 +2419,6 @@ static hipError_t launch2(const StepArgs& a, hipStream_t s, bool reset, hipEvent
   } else {
     TD_STEP_DISPATCH(td_step_kernel, LT, a, TD_LAUNCH);
   }
-#undef TD_LAUNCH
-#undef TD_LAUNCH2
   return hipGetLastError();
 }
 
@@ -2358,6 +2438,7 @@ static int resident3(const StepArgs& a, int cus, int waves) {
 }
 
 int step_resident_boards(const StepArgs& a, int cus, int waves) {
+  if (a.obs_f16) return step_resident_boards_f16(a, cus, waves);
   switch (a.L) {
     case 10: return resident3<10>(a, cus, waves);
     case 20: return resident3<20>(a, cus, waves);
@@ -2367,6 +2448,7 @@ int step_resident_boards(const StepArgs& a, int cus, int waves) {
 }
 
 hipError_t launch_step(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0, hipEvent_t ev1) {
+  if (a.obs_f16 && !reset) return launch_step_f16(a, s, ev0, ev1);  // (the reset kernels branch on the format)
   switch (a.L) {
     case 10: return launch2<10>(a, s, reset, ev0, ev1);
     case 20: return launch2<20>(a, s, reset, ev0, ev1);
@@ -2431,5 +2513,8 @@ hipError_t launch_refill(const StepArgs& a, hipStream_t s, int guard) {
   }
   return hipGetLastError();
 }
+#endif  // TD_STEP_F16_UNIT
+#undef TD_LAUNCH
+#undef TD_LAUNCH2
 
 }  // namespace td

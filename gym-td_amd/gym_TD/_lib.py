@@ -19,6 +19,7 @@ OPP_WORDS = 626
 HDR_BYTES = 96
 ABI_VERSION = 3  # include/tdstep.h TD_ABI_VERSION
 STEP_KERNELS = {"auto": 0, "large": 1, "small": 2, "small2": 3}  # enum td_step_kernel_kind
+OBS_F32, OBS_F16 = 0, 1  # enum td_obs_format
 
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -106,6 +107,9 @@ def _load():
         "td_episode_records": (ctypes.c_int, [c_vp, c_vp, c_vp]),
         "td_opponent": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_u8p, c_vp]),
         "td_set_refill_interval": (ctypes.c_int, [c_vp, ctypes.c_int]),
+        "td_set_obs_format": (ctypes.c_int, [c_vp, ctypes.c_int]),
+        "td_obs_format": (ctypes.c_int, [c_vp]),
+        "td_obs_bytes": (ctypes.c_size_t, [c_vp]),
         "td_step_kernel": (ctypes.c_int, [c_vp]),
         "td_step_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_config_epoch": (ctypes.c_int, [c_vp]),

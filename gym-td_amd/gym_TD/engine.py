@@ -44,7 +44,9 @@ class _DeviceBlock(object):
             pass
 
 
-_TYPESTR = {torch.float32: "<f4", torch.int64: "<i8"}
+_TYPESTR = {torch.float32: "<f4", torch.float16: "<f2", torch.int64: "<i8"}
+# observation dtype -> enum td_obs_format (td_set_obs_format)
+OBS_FORMATS = {torch.float32: _lib.OBS_F32, torch.float16: _lib.OBS_F16}
 
 
 # The engine's observation in physically contiguous device memory or a plain allocation.
@@ -127,11 +129,19 @@ class TDEngine(object):
           right after the step that ends the episode, in stream order).
     step_kernel: 'auto' (td_create's rule by batch size), 'large', 'small' or 'small2'
           (td_set_step_kernel; the three give the same results).
+    obs_dtype: torch.float32 (default) or torch.float16: the element of ``obs``.  The
+          float16 observation is the float32 one rounded to nearest-even, written by the
+          step kernels themselves (td_set_obs_format): half the step's store stream and
+          half the policy's read stream.  Everything else is unchanged ('auto' may pick
+          another step kernel for the narrower stream; the results do not depend on it).
     """
 
     def __init__(self, map_size, n_boards, mode="def", multi_action=None, difficulty=1, device=None,
                  np_seeds=None, py_seeds=None, autoreset=True, info=True, cfg=None, hp=None, host_io=False,
-                 random_agent=True, step_kernel="auto"):
+                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32):
+        if obs_dtype not in OBS_FORMATS:  # (before td_create: no device is touched)
+            raise ValueError("obs_dtype must be torch.float32 or torch.float16, not %r" % (obs_dtype,))
+        self.obs_dtype = obs_dtype
         hp = hp or P.hyper_parameters
         if multi_action is None:
             multi_action = bool(hp.allow_multiple_actions)
@@ -160,8 +170,11 @@ class TDEngine(object):
         zeros = (lambda shape, dtype: torch.zeros(shape, dtype=dtype).pin_memory()) if self.host_io else \
             (lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev))
         # the observation, the step's write stream: contiguous device memory (td_alloc_device)
-        self.obs = zeros((B, _lib.NCH, L, L), torch.float32) if self.host_io else \
-            device_zeros((B, _lib.NCH, L, L), torch.float32, self.device)
+        self.obs = zeros((B, _lib.NCH, L, L), obs_dtype) if self.host_io else \
+            device_zeros((B, _lib.NCH, L, L), obs_dtype, self.device)
+        if obs_dtype != torch.float32:
+            _lib.check(_lib.lib.td_set_obs_format(h, OBS_FORMATS[obs_dtype]))
+        assert _lib.lib.td_obs_bytes(h) == self.obs.numel() * self.obs.element_size()
         # how the observation was allocated (bench.py keys PMC traffic records by it)
         self.obs_alloc = "host" if self.host_io else "contiguous" if getattr(self.obs, "_td_contig", False) else "plain"
         self.reward = zeros(B, torch.float64)
@@ -440,6 +453,24 @@ class TDEngine(object):
         if kind not in _lib.STEP_KERNELS:
             raise ValueError("step kernel must be one of %s" % sorted(_lib.STEP_KERNELS))
         _lib.check(_lib.lib.td_set_step_kernel(self._h, _lib.STEP_KERNELS[kind]))
+
+    def set_obs_dtype(self, obs_dtype, obs=None):
+        """Switch the observation's element between steps (td_set_obs_format): ``obs`` is
+        the new buffer (B, 45, L, L) of that dtype, a fresh one if None.  No board state
+        changes; the next step or reset writes the observation in the new form."""
+        if obs_dtype not in OBS_FORMATS:
+            raise ValueError("obs_dtype must be torch.float32 or torch.float16, not %r" % (obs_dtype,))
+        shape = (self.B, _lib.NCH, self.L, self.L)
+        if obs is None:
+            obs = torch.zeros(shape, dtype=obs_dtype).pin_memory() if self.host_io else \
+                device_zeros(shape, obs_dtype, self.device)
+        if obs.dtype != obs_dtype or tuple(obs.shape) != shape or not obs.is_contiguous():
+            raise ValueError("obs must be a contiguous %r tensor of shape %r" % (obs_dtype, shape))
+        _lib.check(_lib.lib.td_set_obs_format(self._h, OBS_FORMATS[obs_dtype]))
+        self.obs_dtype, self.obs = obs_dtype, obs
+        self._io.obs = obs.data_ptr()
+        if self.host_io:
+            self.np.obs = obs.numpy()
 
     @property
     def step_kernel(self):

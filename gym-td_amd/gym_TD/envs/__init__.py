@@ -322,19 +322,22 @@ class TDVecEnv(object):
     followed by the mask kernel, and ``infos['action_mask']`` (the side that acts; the
     defender's in TD-2p) and ``infos['action_mask_attacker']`` (TD-atk, TD-2p) hold the legal actions
     of the state the step left (TDEngine.action_mask); after reset(), ``action_masks()``.
+    ``obs_dtype=torch.float16``: the observation as float16 (TDEngine's ``obs_dtype``).
     """
 
     def __init__(self, map_size, num_envs, mode="def", difficulty=1, multi_action=None, seed=0, global_offset=0,
-                 device=None, info=True, autoreset=True, host_io=False, random_agent=True, action_mask=False):
+                 device=None, info=True, autoreset=True, host_io=False, random_agent=True, action_mask=False,
+                 obs_dtype=torch.float32):
         self.map_size, self.num_envs, self.mode = int(map_size), int(num_envs), mode
         self.with_action_mask = bool(action_mask)
         self._masks = None
         seeds = np.arange(num_envs, dtype=np.int64) + int(seed) + int(global_offset)
         self.engine = TDEngine(map_size, num_envs, mode, multi_action, difficulty, device=device,
                                np_seeds=seeds, py_seeds=seeds, autoreset=autoreset, info=info, host_io=host_io,
-                               random_agent=random_agent)
+                               random_agent=random_agent, obs_dtype=obs_dtype)
         L = self.map_size
-        self.observation_space = Box(low=0., high=1., shape=(45, L, L), dtype=np.float32)
+        self.observation_space = Box(low=0., high=1., shape=(45, L, L),
+                                     dtype=np.float16 if obs_dtype == torch.float16 else np.float32)
         dspace = (Box(low=0., high=2., shape=(6, L, L), dtype=np.int64) if self.engine.multi
                   else Discrete(L * L * 6 + 1))
         aspace = Box(low=0, high=4, shape=(3, 8), dtype=np.int64)

@@ -40,10 +40,12 @@ class VectorEnv(object):
     Seeds: env i uses seed ``seed + i`` for its layout stream and its built-in
     opponent's stream (``seed`` None: 0).  ``fixed_seed`` is not supported here
     (every auto-reset draws the env's next layout); the single-env classes support it.
+    ``obs_dtype``: ``np.float32`` (default) or ``np.float16`` (or the torch dtypes): the
+    observations' element, written in that form by the step kernels.
     """
 
     def __init__(self, env_id, num_envs, map_size=None, difficulty=1, seed=None, fixed_seed=False, device=None,
-                 random_agent=True):
+                 random_agent=True, obs_dtype=np.float32):
         if fixed_seed:
             raise NotImplementedError("fixed_seed=True: use the single-env classes (gym_TD.envs.TDDefense ...)")
         self.kind, self.map_size = _parse(env_id, map_size)
@@ -54,8 +56,14 @@ class VectorEnv(object):
         self._difficulty = difficulty
         # host_io: the kernels write the numpy outputs straight into pinned host memory
         self._random_agent = bool(random_agent)
+        if not isinstance(obs_dtype, torch.dtype):  # a numpy dtype (or its name)
+            name = np.dtype(obs_dtype).name
+            if name not in ("float32", "float16"):
+                raise ValueError("obs_dtype must be float32 or float16, not %r" % (obs_dtype,))
+            obs_dtype = getattr(torch, name)
         self.vec = _envs.TDVecEnv(self.map_size, self.num_envs, self.kind, difficulty=difficulty, seed=self._seed,
-                                  device=device, info=True, host_io=True, random_agent=self._random_agent)
+                                  device=device, info=True, host_io=True, random_agent=self._random_agent,
+                                  obs_dtype=obs_dtype)
         self.observation_space = self.vec.observation_space
         self.single_action_space = self.vec.action_space
         self.action_space = self.vec.action_space

@@ -114,6 +114,33 @@ typedef struct td_step_io {
 
 typedef struct td_handle td_handle;
 
+/* The observation's element, per engine.  TD_OBS_F32 (the default): float [B][45][L][L].
+ * TD_OBS_F16: IEEE binary16, _Float16 [B][45][L][L], dense, same index order -- each value
+ * is the float32 value of the default format rounded to nearest-even (one conversion in
+ * front of the store; the board work and the channel arithmetic are the same, and every
+ * other output is unchanged).  After td_set_obs_format(h, TD_OBS_F16) every entry point
+ * that writes an observation -- td_step, its auto-reset, the reset kernel behind a step
+ * with random_agent = 0, td_reset, td_reset_layouts -- takes its `obs` pointer (declared
+ * float* here and in td_step_io, whose layout does not change) to be that _Float16 array
+ * of td_obs_bytes(h) bytes.
+ *   Alignment: 2 B is enough.  An 8-B-aligned buffer takes the line-aligned store path at
+ * L = 10 / 20 / 30 (8-B stores, one quad of cells per lane) and the small kernels; an
+ * 8-B-aligned buffer at any other L with L^2 % 4 == 0 the quad path of the generic kernel;
+ * anything else the per-element path (same bytes, slower).  (float32: 16 B, as td_step.)
+ *   td_set_obs_format synchronises the device first, as the mode setters do, and may be
+ * called at any time between steps; it changes no board state.  A kernel kind forced
+ * with td_set_step_kernel stays; TD_KERNEL_AUTO is resolved again for the new format (with
+ * half the bytes to store, 10x10 boards above half a round step fastest on SMALL: the
+ * boards in flight bound the step, not the store stream).  The write-through store policy
+ * follows the new byte size, and td_step_kernel_name
+ * returns "td_step_kernel_f16<...>", "td_step_kernel_small_f16<...>" or
+ * "td_step_kernel_small2_f16<...>" (the float32 kernels keep their names).  An unknown fmt
+ * returns < 0 and changes nothing.  td_obs_bytes: B * 45 * L * L * element size. */
+enum td_obs_format { TD_OBS_F32 = 0, TD_OBS_F16 = 1 };
+int td_set_obs_format(td_handle* h, int fmt);
+int td_obs_format(td_handle* h);
+size_t td_obs_bytes(td_handle* h);
+
 int td_abi_version(void);
 /* sizeof(td_step_io) as this library was built (120 on LP64 at ABI 3). */
 int td_step_io_size(void);
@@ -252,9 +279,10 @@ int td_action_mask(td_handle* h, const td_mask_io* io, void* stream);
  *                    round, SMALL2 again above that -- at any batch for single-action TD-def
  *                    at L = 10, up to 3 rounds for the other L = 10 modes, 10 rounds at
  *                    L = 30 (single-action) and 8 rounds for TD-2p multi-action at L = 20 --
- *                    else LARGE (L = 10 / 20 / 30; other L only have LARGE).
- * The small kernels need a 16-B-aligned observation buffer; a td_step with any other
- * buffer runs LARGE.  (Forcing a kind is a test hook: td_set_step_kernel, td_diag.h.)
+ *                    else LARGE (L = 10 / 20 / 30; other L only have LARGE).  With
+ *                    TD_OBS_F16 at L = 10: SMALL2 up to half a round, SMALL above.
+ * The small kernels need a 16-B-aligned observation buffer (8-B-aligned with TD_OBS_F16);
+ * a td_step with any other buffer runs LARGE.  (Forcing a kind is a test hook: td_set_step_kernel, td_diag.h.)
  * td_step_kernel returns the resolved kind, td_step_kernel_name the
  * kernel's name as rocprofv3 shows it ("td_step_kernel_small<10, 0, false>": L, mode,
  * multi-action scan). */

@@ -150,6 +150,28 @@ int main(int argc, char** argv) {
     CK(hipFree(buf));
     return 0;
   }
+  // argv[1] = "f16": the float16 observation's stream (9,000 / 36,000 / 81,000 B per board)
+  // stored 8 B per lane (one unit of write_obs_lines<_Float16>) or 16 B per lane (two units;
+  // a board that starts 8 B off a 16-B boundary loses its first and last 8 B here)
+  if (argc > 1 && argv[1][0] == 'f') {
+    const int shapes[3][2] = {{10, 65536}, {20, 16384}, {30, 16384}};
+    for (const auto& sh : shapes) {
+      const int L = sh[0], nb = sh[1], rowb = 45 * L * L * 2;
+      const size_t bytesz = (size_t)nb * rowb + 4096;
+      char* buf = nullptr;
+      CK(hipExtMallocWithFlags((void**)&buf, bytesz, hipDeviceMallocContiguous));
+      CK(hipMemset(buf, 0, bytesz));
+      const double bytes = (double)nb * rowb;
+      const double w8 = timed([&] { hipLaunchKernelGGL((obs_shape<8, 2, 1, 1>), dim3(nb), dim3(64), 0, 0, buf, nb, rowb); }, bytes);
+      const double w16 = timed([&] { hipLaunchKernelGGL((obs_shape<16, 2, 1, 1>), dim3(nb), dim3(64), 0, 0, buf, nb, rowb); }, bytes);
+      const double w8x2 = timed([&] { hipLaunchKernelGGL((obs_shape<8, 2, 1, 2>), dim3(nb), dim3(128), 0, 0, buf, nb, rowb); }, bytes);
+      std::printf("float16 %dx%d %5d boards (%7.1f MB) | 8 B per lane %.2f TB/s (%.1f us) | 16 B per lane %.2f TB/s (%.1f us) | "
+                  "8 B per lane, two waves per board %.2f TB/s\n",
+                  L, L, nb, bytes / 1e6, w8, bytes / (w8 * 1e12) * 1e6, w16, bytes / (w16 * 1e12) * 1e6, w8x2);
+      CK(hipFree(buf));
+    }
+    return 0;
+  }
   // argv[1] = 20 or 30: 16,384 boards of a 20x20 (72,000 B) or 30x30 (162,000 B) observation
   if (argc > 1) {
     const int L = std::atoi(argv[1]), nb = 16384, rowb = 45 * L * L * 4;
