@@ -109,6 +109,24 @@ constexpr uint64_t kChEnemy = 0xFFFFull << 25;
 constexpr uint64_t kChAll = (1ull << NCH) - 1;
 constexpr uint64_t kChConst = kChAll & ~(kChBin | kChD9 | kChEnemy);
 
+// Dirty classes of the observation (td_retain_obs): the channels of one class change
+// together, and a step that found none of a window's classes dirty leaves the window as
+// its last write left it.  STATIC: the layout (roads, end, starts, distance, channel 10),
+// new only with a new episode; LP: channel 5 (a leak); TOWER: buildable, tower level / type
+// (the tower list changed); COST: channels 21-24 (cost_def crossed a tower cost); ENEMY:
+// the enemy planes (an enemy before or after the step); ALWAYS: costs, progress, channels
+// 41-44.
+enum : uint32_t { OD_STATIC = 1u, OD_LP = 2u, OD_TOWER = 4u, OD_COST = 8u, OD_ENEMY = 16u, OD_ALWAYS = 32u, OD_ALL = 63u };
+__host__ __device__ constexpr uint32_t obs_dirty_class(int ch) {
+  return ch == 5 ? OD_LP
+       : (ch <= 10) ? OD_STATIC
+       : (ch <= 13) ? OD_ALWAYS
+       : (ch <= 20) ? OD_TOWER
+       : (ch <= 24) ? OD_COST
+       : (ch <= 40) ? OD_ENEMY
+       : OD_ALWAYS;
+}
+
 // The step wave of board b found layout `head` unpublished at the episode end.  If a
 // refill wave holds the board's claim it is drawing exactly this layout (an empty ring
 // is urgent: its draw runs to the end): wait for the tag, bounded (1 s; a wait that gives

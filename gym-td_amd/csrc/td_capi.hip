@@ -16,6 +16,7 @@
 #include <string>
 #include <thread>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/tdstep.h"
@@ -125,6 +126,12 @@ struct td_handle {
   int edge_wt = 2;  // observation lines shared with a neighbour: plain write-back stores, merged in the XCD's L2
                     // (1.088x vs 1.093x the algorithmic bytes at 65,536 boards, step time +-0, profiles/r04/s20);
                     // 1: write-through (sc1), the reference form of tests/test_gpu_store_policy.py
+  // td_retain_obs: the buffer the caller leaves to this handle's own writes, and whether it
+  // holds every board's observation as this handle's last write left it (obs_touch clears it)
+  const void* retained = nullptr;
+  bool retained_valid = false;     // every board's is known to be there
+  std::vector<uint8_t> obs_known;  // [B] board b's is (a reset into the buffer wrote it, or a step)
+  int n_known = 0;
 };
 
 namespace {
@@ -200,9 +207,51 @@ static hipError_t dev_malloc(void** p, size_t bytes, bool contiguous, bool* gran
   return hipMalloc(p, bytes);
 }
 
-// Live td_alloc_device blocks and how each was placed (td_alloc_is_contiguous).
+// Live td_alloc_device blocks: how each was placed (td_alloc_is_contiguous) and its size.
+struct Block { bool contiguous; size_t bytes; };
 std::mutex g_blocks_mu;
-std::unordered_map<const void*, bool> g_blocks;
+std::unordered_map<const void*, Block> g_blocks;
+// Live handles (td_free_device drops the retention of a buffer inside the freed block).
+std::mutex g_handles_mu;
+std::unordered_set<td_handle*> g_handles;
+
+// Some board's observation would now differ from what the retained buffer holds, and
+// nothing wrote it there: the next step writes every byte (td_retain_obs).
+void obs_touch(td_handle* h) {
+  h->retained_valid = false;
+  if (h->n_known) std::fill(h->obs_known.begin(), h->obs_known.end(), (uint8_t)0);
+  h->n_known = 0;
+}
+// Board b's observation was just written whole into the retained buffer.
+void obs_mark(td_handle* h, int b) {
+  if (h->obs_known.size() != (size_t)h->B) h->obs_known.assign((size_t)h->B, 0);
+  if (!h->obs_known[(size_t)b]) {
+    h->obs_known[(size_t)b] = 1;
+    h->n_known += 1;
+  }
+  h->retained_valid = h->n_known == h->B;
+}
+// Every board's was (a step into the retained buffer).
+void obs_mark_all(td_handle* h) {
+  h->obs_known.assign((size_t)h->B, 1);
+  h->n_known = h->B;
+  h->retained_valid = true;
+}
+// A reset that writes into `obs`: the boards it resets are written whole.  Into the
+// retained buffer that keeps it current; anywhere else (or nowhere) leaves it behind.
+bool obs_reset_into(td_handle* h, const void* obs) {
+  const bool mine = obs && obs == h->retained;
+  if (!mine) obs_touch(h);
+  return mine;
+}
+// A call that returns early with an error leaves the retained buffer behind.
+struct ObsGuard {
+  td_handle* h;
+  bool ok = false;
+  ~ObsGuard() {
+    if (!ok) obs_touch(h);
+  }
+};
 
 template <class T>
 int dalloc(T** p, size_t n) {
@@ -382,15 +431,31 @@ int td_alloc_device(size_t bytes, int device, int contiguous, void** out) {
     return fail("td_alloc_device: %s", hipGetErrorString(e));
   }
   std::lock_guard<std::mutex> g(g_blocks_mu);
-  g_blocks[*out] = granted;
+  g_blocks[*out] = Block{granted, bytes};
   return 0;
 }
 
 int td_free_device(void* p) {
   if (!p) return 0;
+  size_t bytes = 0;
   {
     std::lock_guard<std::mutex> g(g_blocks_mu);
-    g_blocks.erase(p);
+    auto it = g_blocks.find(p);
+    if (it != g_blocks.end()) {
+      bytes = it->second.bytes;
+      g_blocks.erase(it);
+    }
+  }
+  {  // a later allocation may reuse the address: no handle may take it for the buffer it retained
+    std::lock_guard<std::mutex> g(g_handles_mu);
+    const char* lo = static_cast<const char*>(p);
+    for (td_handle* h : g_handles) {
+      const char* r = static_cast<const char*>(h->retained);
+      if (r && r >= lo && r < lo + std::max<size_t>(bytes, 1)) {
+        h->retained = nullptr;
+        obs_touch(h);
+      }
+    }
   }
   HIP_OK(hipFree(p));
   return 0;
@@ -399,7 +464,7 @@ int td_free_device(void* p) {
 int td_alloc_is_contiguous(const void* p) {
   std::lock_guard<std::mutex> g(g_blocks_mu);
   auto it = g_blocks.find(p);
-  return it == g_blocks.end() ? -1 : it->second ? 1 : 0;
+  return it == g_blocks.end() ? -1 : it->second.contiguous ? 1 : 0;
 }
 
 void td_step_io_init(td_step_io* io) {
@@ -547,11 +612,19 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
   std::vector<uint32_t> seeds(B);
   for (size_t b = 0; b < B; ++b) seeds[b] = (uint32_t)b;
   if (td_seed(h, seeds.data(), seeds.data()) != 0) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
+  {
+    std::lock_guard<std::mutex> g(g_handles_mu);
+    g_handles.insert(h);
+  }
   return h;
 }
 
 void td_destroy(td_handle* h) {
   if (!h) return;
+  {
+    std::lock_guard<std::mutex> g(g_handles_mu);
+    g_handles.erase(h);
+  }
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
   void* dptrs[] = {h->d_cfg, h->d_hdr, h->d_en_lp, h->d_en_mg, h->d_en_inf, h->d_tw_cd, h->d_tw_inf,
@@ -600,6 +673,7 @@ int td_set_config(td_handle* h, const td_config* cfg) {
   HIP_OK(hipMemcpy(h->d_cfg + slot, &d, sizeof d, hipMemcpyHostToDevice));
   h->dcfg = d;
   h->epoch = slot;
+  obs_touch(h);  // channels 21-24 and 41-44 read the current block
   return 0;
 }
 
@@ -720,12 +794,18 @@ int td_reset(td_handle* h, const uint8_t* host_mask, float* obs, void* stream) {
   std::vector<uint8_t> mask((size_t)h->B, 1);
   if (host_mask) std::memcpy(mask.data(), host_mask, (size_t)h->B);
   HIP_OK(hipDeviceSynchronize());
+  const bool mine = obs_reset_into(h, obs);
+  ObsGuard guard{h};
   if (run_reset(h, mask, obs, s)) return -1;
   std::vector<uint8_t> fl((size_t)h->B);
   HIP_OK(hipMemcpy(fl.data(), h->d_fail, (size_t)h->B, hipMemcpyDeviceToHost));
   h->last_reset_failed.clear();
-  for (int b = 0; b < h->B; ++b)
-    if (mask[(size_t)b] && fl[(size_t)b]) h->last_reset_failed.push_back(b);
+  for (int b = 0; b < h->B; ++b) {
+    if (!mask[(size_t)b]) continue;
+    if (fl[(size_t)b]) h->last_reset_failed.push_back(b);
+    else if (mine) obs_mark(h, b);  // (a board whose draw failed keeps its state, and its observation)
+  }
+  guard.ok = true;
   return (int)h->last_reset_failed.size();
 }
 
@@ -743,6 +823,8 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
     if (boards[i] < 0 || boards[i] >= h->B || recs[(size_t)i * h->lw] != TD_LAYOUT_MAGIC)
       return fail("td_reset_layouts: bad board id or layout record %d", i);
   HIP_OK(hipDeviceSynchronize());
+  const bool mine = n > 0 && obs_reset_into(h, obs);
+  ObsGuard guard{h};
   std::vector<int32_t> idx((size_t)h->B, -1);
   for (int i0 = 0; i0 < n; i0 += h->stage_cap) {
     const int m = std::min(h->stage_cap, n - i0);
@@ -761,7 +843,9 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
     HIP_OK(launch_step(a, s, true));
     h->since_guard = kGuardEvery;
     HIP_OK(hipStreamSynchronize(s));
+    for (int i = 0; mine && i < m; ++i) obs_mark(h, boards[i0 + i]);
   }
+  guard.ok = true;
   return 0;
 }
 
@@ -786,6 +870,11 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   a.cooldowns = io->cooldowns;
   a.ep_stats = h->d_epstats;
   a.last_ep = h->d_lastep;
+  // td_retain_obs: a step into the retained buffer may skip what the buffer already holds;
+  // any other step writes every byte and leaves the retained buffer behind.
+  const bool retained = h->retained && (const void*)io->obs == h->retained;
+  a.obs_skip = retained && h->retained_valid ? 1 : 0;
+  ObsGuard guard{h};
   // the refill goes first: it waits for the previous step only, so a board whose ring
   // is dry in this step can wait for it (td_step.hip step_board) without a cycle
   // random_agent=True: layouts are staged ahead by refills on the side streams.
@@ -808,6 +897,9 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   if (h->autoreset && h->opp_np) HIP_OK(launch_autoreset(a, s));
   h->steps += 1;
   h->since_guard += 1;
+  if (!retained) obs_touch(h);
+  else if (!h->retained_valid) obs_mark_all(h);  // every board's observation is in the retained buffer now
+  guard.ok = true;
   return 0;
 }
 
@@ -866,6 +958,7 @@ int td_set_obs_format(td_handle* h, int fmt) {
   if (fmt != TD_OBS_F32 && fmt != TD_OBS_F16) return fail("td_set_obs_format: unknown format %d (TD_OBS_F32 = 0, TD_OBS_F16 = 1)", fmt);
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep the format they were enqueued with
   h->obs_fmt = fmt;
+  obs_touch(h);  // (the same format again too: the caller may have changed the buffer's element)
   return apply_kernel(h, h->kernel_forced ? h->small : auto_kernel(h));
 }
 
@@ -874,6 +967,16 @@ int td_obs_format(td_handle* h) { return h ? h->obs_fmt : fail("NULL handle"); }
 size_t td_obs_bytes(td_handle* h) {
   return h ? (size_t)h->B * NCH * h->NC * (h->obs_fmt == TD_OBS_F16 ? 2u : 4u) : 0;
 }
+
+int td_retain_obs(td_handle* h, const void* obs) {
+  if (!h) return fail("NULL handle");
+  HIP_OK(hipDeviceSynchronize());  // launches already queued keep what they were enqueued with
+  h->retained = obs;
+  obs_touch(h);  // nothing is known of the buffer yet: the next step into it writes every byte
+  return 0;
+}
+
+const void* td_retained_obs(td_handle* h) { return h ? h->retained : nullptr; }
 
 const char* td_step_kernel_name(td_handle* h) { return h ? h->kernel_name.c_str() : ""; }
 
@@ -935,6 +1038,7 @@ int td_opponent(td_handle* h, int side, int level, const uint8_t* host_mask, voi
   HIP_OK(hipMemcpy(h->d_mask, mask.data(), (size_t)h->B, hipMemcpyHostToDevice));
   StepArgs a = base_args(h);
   a.reset_mask = h->d_mask;
+  obs_touch(h);  // enemies, towers and costs change; no observation is written
   HIP_OK(launch_opponent(a, side, level, s));
   HIP_OK(hipStreamSynchronize(s));
   return 0;
@@ -1039,6 +1143,7 @@ int td_import_state(td_handle* h, int b0, int count, const void* host_src) {
     if (x.n_en < 0 || x.n_en > ECAP || x.n_tw < 0 || x.n_tw > TCAP)
       return fail("td_import_state: board %d: %d enemies / %d towers exceed the capacity", b0 + i, x.n_en, x.n_tw);
   }
+  obs_touch(h);
   return state_copy(h, b0, count, const_cast<void*>(host_src), false);
 }
 

@@ -71,6 +71,8 @@ struct StepArgs {
   int xcd_map;   // block i steps board xcd_board(i, B) (else board i)
   int edge_wt;   // observation lines shared with a neighbouring board: 2 plain, 1 write-through (write_obs_lines)
   int obs_f16;   // the observation is _Float16 [B][45][L][L] (td_set_obs_format): the *_f16 step kernels
+  int obs_skip;  // obs is the retained buffer and holds every board's last observation (td_retain_obs): the
+                 // step may leave the windows of clean dirty classes unwritten (write_obs_lines)
 };
 
 constexpr int NXCD = 8;  // XCDs of an MI355X: block i runs on XCD i % 8

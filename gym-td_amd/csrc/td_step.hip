@@ -62,8 +62,10 @@ struct alignas(16) Smem {
       float d9[64];       // channel 9 by distance (road length < 2L <= 64)
     };
   };
-  uint32_t early_go;         // td_step_kernel_small2: the binary-plane windows may be written early
+  uint32_t early_go;         // td_step_kernel_small2: the binary-plane windows may be written early (kEarlyGo | dirty classes)
   int32_t flags0;            // the board's flags as loaded (store_board: is the header's second half dirty?)
+  uint32_t before;           // the board as loaded, for the dirty classes: cost_bits (bits 0-3), an enemy (bit 4)
+  int32_t before_lp;         // ... and its base_LP
   TdDevCfg cfg;           // constant block, staged once per board: per-lane table lookups hit LDS
 };
 
@@ -1131,6 +1133,25 @@ struct ObsWinTab {
     return t;
   }
   static constexpr T tab = make();
+  // The dirty classes (OD_*, td_board.h) whose channels window k overlaps, 8 bits per
+  // window: a step that may skip (StepArgs::obs_skip) writes the window only if one of them
+  // is dirty.  (A window past the board's last unit, at a small `mis`, has none.)
+  static constexpr int WD = (K + 3) / 4;
+  struct D { uint32_t w[UPL][WD]; };
+  static constexpr uint32_t dirty(int mis, int k) {
+    const int ulo = 64 * k - mis, uhi = ulo + 63;
+    const int clo = (ulo < 0 ? 0 : ulo) / Q, chi = (uhi > N4 - 1 ? N4 - 1 : uhi) / Q;
+    uint32_t d = 0;
+    for (int c = clo; c <= chi; ++c) d |= obs_dirty_class(c);
+    return d;
+  }
+  static constexpr D make_d() {
+    D t{};
+    for (int m = 0; m < UPL; ++m)
+      for (int k = 0; k < K; ++k) t.w[m][k / 4] |= dirty(m, k) << (8 * (k % 4));
+    return t;
+  }
+  static constexpr D dtab = make_d();
 };
 
 // The (45, L, L) float32 observation of one board for compile-time L, into a
@@ -1161,9 +1182,14 @@ struct ObsWinTab {
 // OT = _Float16: the same units, windows and classes with 8-B units -- a wave store is
 // 512 B, four whole lines; a board starts at one of 16 unit offsets in its line
 // (ObsWinTab<LT, 16>) and has one window more where N4 + 15 crosses a multiple of 64.
-template <int NC, int LT, int KB = 0, int KE = -1, int G = 4, int PASS = 0, class OT = float>
+//
+// SKIP (td_retain_obs): `dirty` is the board's set of dirty classes (OD_*, wave-uniform); a
+// window none of whose classes is dirty (ObsWinTab::dtab) is left as the last write left
+// it -- skipped before its LDS reads are issued, as PASS skips windows.  A window that is
+// written is written whole, as without SKIP.
+template <int NC, int LT, int KB = 0, int KE = -1, int G = 4, int PASS = 0, class OT = float, bool SKIP = false>
 __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, OT* out, bool any_enemy, bool wt,
-                                                int edge_wt = 1) {
+                                                int edge_wt = 1, uint32_t dirty = OD_ALL) {
   static_assert(LT >= 8, "a 128-B line spans at most two channel planes");
   typedef ObsFmt<OT> F;
   constexpr int UB = F::UB, UPL = F::UPL;
@@ -1183,6 +1209,8 @@ __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, OT*
   typedef Div24<Q, N4 + 64> DivQ;  // unit -> channel (every unit read is in [0, N4))
   // the window's channel class and edge bit (wave-uniform, ObsWinTab)
   auto wclass = [&](int k) { return (ObsWinTab<LT, UPL>::tab.w[mis][k >> 3] >> (4 * (k & 7))) & 7u; };
+  if (SKIP) dirty = __builtin_amdgcn_readfirstlane(dirty);
+  auto wclean = [&](int k) { return SKIP && ((ObsWinTab<LT, UPL>::dtab.w[mis][k >> 2] >> (8 * (k & 3))) & dirty) == 0u; };
   // only a window at either end of the board holds lanes outside it (i < 0, i >= N4):
   // clamp there, so every lane reads LDS inside the board image
   auto unit = [&](int i, uint32_t wc) { return (wc & 4u) ? (i < 0 ? 0 : (i > N4 - 1 ? N4 - 1 : i)) : i; };
@@ -1195,6 +1223,7 @@ __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, OT*
       if ((K - KB) % G == 0 || k < K) {
         const uint32_t wc = wclass(k);
         if (PASS != 0 && (((wc & 3u) == 0) != (PASS == 1))) continue;  // wave-uniform
+        if (wclean(k)) continue;
         const int i = unit(i0 + 64 * k, wc);
         const int ch = DivQ::div(i), q = i - ch * Q;
         A[j] = *reinterpret_cast<const uint4*>(sb + o_cell + 16 * q);
@@ -1218,6 +1247,7 @@ __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, OT*
       if (!((K - KB) % G == 0 || k < K)) continue;
       const uint32_t wc = wclass(k);
       if (PASS != 0 && (((wc & 3u) == 0) != (PASS == 1))) continue;
+      if (wclean(k)) continue;
       const bool edge = (wc & 4u) != 0;  // the window holds a line shared with a neighbour
       const int i = i0 + 64 * k;
       const int ch = DivQ::div(unit(i, wc));
@@ -1476,6 +1506,7 @@ struct alignas(16) StepOut {
                  // half of the late windows, 2 store only (an auto-reset board: the stepping wave writes every window)
   uint32_t any;  // the board has enemies (enemy windows read the group statistics)
   uint32_t hdr_hi;  // the header's second half changed (store_board): 6 lanes store it, else 3
+  uint32_t dirty;   // the observation's dirty classes (obs_dirty): the late windows the second wave writes
 };
 
 __device__ __forceinline__ void store_outputs(const StepArgs& a, int b, double reward, double ep_ret, int64_t real_def,
@@ -1693,6 +1724,27 @@ constexpr int obs_late_half() {
   return K;
 }
 
+// The four bits of channels 21-24 (channel_scalars): cost_def reaches tower t's cost.
+__device__ __forceinline__ uint32_t cost_bits(double cost_def, const TdDevCfg& C) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) m |= (cost_def >= C.t_price[t][0]) ? (1u << t) : 0u;
+  return m;
+}
+
+// The dirty classes of a board's observation after its step (td_retain_obs), against the
+// board as loaded (Smem::before, before_lp).  Every class unless the step may skip
+// (StepArgs::obs_skip) and the board kept its episode: a new episode has a new layout.
+// tw_dirty: the tower list changed (it decides the tower-word stores too).
+template <int NC>
+__device__ __forceinline__ uint32_t obs_dirty(const Smem<NC>& S, const U& u, const TdDevCfg& C, bool skip, bool was_reset) {
+  if (!skip || was_reset) return OD_ALL;
+  const uint32_t bf = S.before;
+  return OD_ALWAYS | (u.tw_dirty ? OD_TOWER : 0u) | (u.base_LP != S.before_lp ? OD_LP : 0u) |
+         (cost_bits(u.cost_def, C) != (bf & 15u) ? OD_COST : 0u) | (((bf & 16u) != 0u || u.n > 0) ? OD_ENEMY : 0u);
+}
+constexpr uint32_t kEarlyGo = 0x80000000u;  // Smem::early_go: the second wave's early pass may run (| its dirty classes)
+
 // SPLIT: the board's workgroup has a second wave (td_step_kernel_small2) that waits at
 // the one workgroup barrier of this path and then writes the second half of the
 // observation windows.
@@ -1705,7 +1757,13 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
   U u;
   constexpr int PF = SMALL ? PF_SMALL : PF_LARGE;
   load_board<NC, PF, PF>(S, u, x, a, b, P);
-  const int64_t act_in = (int64_t)(((uint64_t)lane_word(P.w, PF_ACT + 1) << 32) | lane_word(P.w, PF_ACT));
+  // what the dirty classes compare with after the step (obs_dirty), kept in LDS: the small
+  // kernels have no SGPR to carry it across the step
+  if (x.lane == 0) {
+    S.before = cost_bits(u.cost_def, C) | (u.n > 0 ? 16u : 0u);
+    S.before_lp = u.base_LP;
+  }
+  const int64_t act_in =(int64_t)(((uint64_t)lane_word(P.w, PF_ACT + 1) << 32) | lane_word(P.w, PF_ACT));
   // built-in opponent stream: position, lazy-twist boundary and the next draws
   // (pre-computed by the previous step) come from the board's hot record
   WaveMt R{opp, lane_word(P.w, PF_HOT + 0), lane_word(P.w, PF_HOT + 1)};
@@ -1810,7 +1868,9 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
   }
   wsync();
   if constexpr (SPLIT) {  // (A): the second wave writes the binary-plane windows while this one steps
-    if (x.lane == 0) S.early_go = 1u;
+    // (its windows hold static and tower planes only: with the skip, the tower windows of a
+    // board whose tower list changed -- a board that auto-resets rewrites every window below)
+    if (x.lane == 0) S.early_go = kEarlyGo | (a.obs_skip ? (u.tw_dirty ? (uint32_t)OD_TOWER : 0u) : (uint32_t)OD_ALL);
     __syncthreads();
   }
 
@@ -1884,6 +1944,7 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     sst(&hot[3], R.cbase);
   }
   if (refill && x.lane < HOT_CACHE) sst(&hot[4 + x.lane], R.cache);
+  const uint32_t dirty = obs_dirty(S, u, C, a.obs_skip != 0, was_reset);
   if constexpr (SPLIT) {
     // (B) the second wave's early pass has landed; it takes the board and the outputs
     // and stores them while this wave computes the statistics and broadcast channels;
@@ -1895,7 +1956,7 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
       so->reward = reward; so->ep_ret = ep_ret; so->real_def = real_def;
       so->ep_steps = ep_steps; so->fail_def = fail_def;
       so->done = done ? 1u : 0u; so->win = (uint32_t)(int32_t)win; so->allow = allow; so->cool = cool;
-      so->go = was_reset ? 2u : 1u; so->any = u.n > 0 ? 1u : 0u;
+      so->go = was_reset ? 2u : 1u; so->any = u.n > 0 ? 1u : 0u; so->dirty = dirty;
       so->hdr_hi = (was_reset || done || u.flags != S.flags0) ? 1u : 0u;
     }
     __syncthreads();
@@ -1903,7 +1964,10 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     channel_scalars(S, u, x);
     __syncthreads();
     if (was_reset) write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
-    else write_obs_lines<NC, LT, 0, obs_late_half<LT, OT>(), 4, 2, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+    // (every class dirty -- a step that may not skip: the writer without the skip's table reads
+    // and tests, 203 vs 207 us at 65,536 boards, 32.0 vs 34.9 at 8,192; profiles/obs_retain/two_path_ab.log)
+    else if (dirty == OD_ALL) write_obs_lines<NC, LT, 0, obs_late_half<LT, OT>(), 4, 2, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+    else write_obs_lines<NC, LT, 0, obs_late_half<LT, OT>(), 4, 2, OT, true>(S, x.lane, obs, u.n > 0, wt, a.edge_wt, dirty);
   } else {
     enemy_stats(S, u, x);  // no-op for a board without enemies (e.g. just reset)
     channel_scalars(S, u, x);
@@ -1916,7 +1980,8 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     // the observation last: nothing of the step is live any more, the writer has the registers
     if constexpr (LT != 0) {
       if ((reinterpret_cast<uintptr_t>(a.obs) & (ObsFmt<OT>::UB - 1)) == 0) {
-        write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+        if (dirty == OD_ALL) write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
+        else write_obs_lines<NC, LT, 0, -1, 4, 0, OT, true>(S, x.lane, obs, u.n > 0, wt, a.edge_wt, dirty);
       } else {
         write_obs<NC, LT, OT>(S, x, obs, u.n > 0);
       }

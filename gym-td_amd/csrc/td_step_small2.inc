@@ -34,8 +34,9 @@ __global__ __launch_bounds__(128) TD_SMALL2_ATTR void TD_SMALL2_NAME(StepArgs a_
     if constexpr (SCAN2) {  // the real actions, beside the step (grp[1] is not touched before (B))
       if (S.early_go && a.real_def) scan_write_real(S, lane, NC, a.real_def + (size_t)b * 6 * NC);
     }
-    if (S.early_go) {
-      write_obs_lines<NC, LT, 0, -1, 4, 1, OT>(S, lane, obs, false, a.obs_wt != 0, a.edge_wt);
+    if (const uint32_t early = S.early_go & OD_ALL) {  // (kEarlyGo alone: no binary-plane window is dirty)
+      if (early == OD_ALL) write_obs_lines<NC, LT, 0, -1, 4, 1, OT>(S, lane, obs, false, a.obs_wt != 0, a.edge_wt);
+      else write_obs_lines<NC, LT, 0, -1, 4, 1, OT, true>(S, lane, obs, false, a.obs_wt != 0, a.edge_wt, early);
       // landed before (B): after an auto-reset the first wave rewrites these windows
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -49,8 +50,12 @@ __global__ __launch_bounds__(128) TD_SMALL2_ATTR void TD_SMALL2_NAME(StepArgs a_
       store_outputs(a, b, SO, lane);
     }
     __syncthreads();  // (C) statistics and broadcast channels in LDS
-    if (go == 1u)
-      write_obs_lines<NC, LT, obs_late_half<LT, OT>(), -1, 4, 2, OT>(S, lane, obs, SO.any != 0u, a.obs_wt != 0,
-                                                                    a.edge_wt);
+    if (go == 1u) {
+      if (SO.dirty == OD_ALL)
+        write_obs_lines<NC, LT, obs_late_half<LT, OT>(), -1, 4, 2, OT>(S, lane, obs, SO.any != 0u, a.obs_wt != 0, a.edge_wt);
+      else
+        write_obs_lines<NC, LT, obs_late_half<LT, OT>(), -1, 4, 2, OT, true>(S, lane, obs, SO.any != 0u, a.obs_wt != 0,
+                                                                            a.edge_wt, SO.dirty);
+    }
   }
 }

@@ -110,6 +110,8 @@ def _load():
         "td_set_obs_format": (ctypes.c_int, [c_vp, ctypes.c_int]),
         "td_obs_format": (ctypes.c_int, [c_vp]),
         "td_obs_bytes": (ctypes.c_size_t, [c_vp]),
+        "td_retain_obs": (ctypes.c_int, [c_vp, c_vp]),
+        "td_retained_obs": (c_vp, [c_vp]),
         "td_step_kernel": (ctypes.c_int, [c_vp]),
         "td_step_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_config_epoch": (ctypes.c_int, [c_vp]),

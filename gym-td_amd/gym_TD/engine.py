@@ -79,6 +79,24 @@ def _contig_obs(nbytes):
     return CONTIG_OBS
 
 
+# The engine's device observation is retained (td_retain_obs): a step writes only the
+# windows of a board's observation that may have changed since the step before.
+# TD_RETAIN_OBS=0 (or false / no / off) is the A/B switch: every engine writes every byte,
+# whatever its retain_obs argument; 1 / unset leaves the argument in charge; any other
+# value warns once and does the same.
+def _parse_retain_obs(v):
+    v = (v or "1").strip().lower()
+    if v in ("0", "false", "no", "off"):
+        return False
+    if v not in ("1", "true", "yes", "on"):
+        import warnings
+        warnings.warn("TD_RETAIN_OBS=%r is not 0 / 1 / true / false: using 1" % v, RuntimeWarning)
+    return True
+
+
+RETAIN_OBS = _parse_retain_obs(os.environ.get("TD_RETAIN_OBS"))
+
+
 def device_zeros(shape, dtype, device, contiguous=None):
     """A zeroed device tensor in td_alloc_device memory (contiguous: physically contiguous
     where the driver can give it); torch.zeros if torch cannot adopt the block."""
@@ -134,14 +152,23 @@ class TDEngine(object):
           step kernels themselves (td_set_obs_format): half the step's store stream and
           half the policy's read stream.  Everything else is unchanged ('auto' may pick
           another step kernel for the narrower stream; the results do not depend on it).
+    retain_obs: True (default): the engine's device observation is retained
+          (td_retain_obs) -- a step leaves unwritten what its previous step already left
+          there, so ``obs`` must only be read: code that writes into the tensor ``step``
+          returns (in-place normalisation, masking) must work on a copy, or construct
+          with retain_obs=False.  Ignored with host_io; TD_RETAIN_OBS=0 turns it off
+          for every engine.
     """
 
     def __init__(self, map_size, n_boards, mode="def", multi_action=None, difficulty=1, device=None,
                  np_seeds=None, py_seeds=None, autoreset=True, info=True, cfg=None, hp=None, host_io=False,
-                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32):
+                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32, retain_obs=True):
         if obs_dtype not in OBS_FORMATS:  # (before td_create: no device is touched)
             raise ValueError("obs_dtype must be torch.float32 or torch.float16, not %r" % (obs_dtype,))
+        if not isinstance(retain_obs, (bool, np.bool_)):
+            raise ValueError("retain_obs must be True or False, not %r" % (retain_obs,))
         self.obs_dtype = obs_dtype
+        self.retain_obs = bool(retain_obs) and RETAIN_OBS and not host_io
         hp = hp or P.hyper_parameters
         if multi_action is None:
             multi_action = bool(hp.allow_multiple_actions)
@@ -175,6 +202,7 @@ class TDEngine(object):
         if obs_dtype != torch.float32:
             _lib.check(_lib.lib.td_set_obs_format(h, OBS_FORMATS[obs_dtype]))
         assert _lib.lib.td_obs_bytes(h) == self.obs.numel() * self.obs.element_size()
+        self._arm_retain(True)
         # how the observation was allocated (bench.py keys PMC traffic records by it)
         self.obs_alloc = "host" if self.host_io else "contiguous" if getattr(self.obs, "_td_contig", False) else "plain"
         self.reward = zeros(B, torch.float64)
@@ -219,6 +247,14 @@ class TDEngine(object):
         P._live.add(self)
 
     # ------------------------------------------------------------------ setup
+    def _arm_retain(self, own):
+        """Retain ``self.obs`` if the engine allocated it as a td_alloc_device block (whose
+        release drops the retention, so a reused address is never taken for it); a
+        caller's buffer, or one torch's allocator may hand out again, is written whole."""
+        if self.retain_obs:
+            mine = own and getattr(self.obs, "_td_block", False)
+            _lib.check(_lib.lib.td_retain_obs(self._h, self.obs.data_ptr() if mine else None))
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.lib.td_destroy(self._h)
@@ -329,7 +365,9 @@ class TDEngine(object):
         """One step of every board; returns (obs, reward, done) device tensors.
 
         The tensors are the engine's own buffers, overwritten by the next step
-        (clone them to keep a history)."""
+        (clone them to keep a history).  The returned obs tensor is the engine's buffer:
+        read it, do not write it -- with retain_obs (the default) the next step leaves
+        unwritten whatever it knows its last write left there."""
         io = self._io
         keep = []
         if self.host_io:
@@ -461,6 +499,7 @@ class TDEngine(object):
         if obs_dtype not in OBS_FORMATS:
             raise ValueError("obs_dtype must be torch.float32 or torch.float16, not %r" % (obs_dtype,))
         shape = (self.B, _lib.NCH, self.L, self.L)
+        own = obs is None
         if obs is None:
             obs = torch.zeros(shape, dtype=obs_dtype).pin_memory() if self.host_io else \
                 device_zeros(shape, obs_dtype, self.device)
@@ -469,6 +508,7 @@ class TDEngine(object):
         _lib.check(_lib.lib.td_set_obs_format(self._h, OBS_FORMATS[obs_dtype]))
         self.obs_dtype, self.obs = obs_dtype, obs
         self._io.obs = obs.data_ptr()
+        self._arm_retain(own)
         if self.host_io:
             self.np.obs = obs.numpy()
 

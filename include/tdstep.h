@@ -141,6 +141,36 @@ int td_set_obs_format(td_handle* h, int fmt);
 int td_obs_format(td_handle* h);
 size_t td_obs_bytes(td_handle* h);
 
+/* Retained observation (off by default: td_retain_obs(h, NULL)).  The caller promises
+ * that from now on the td_obs_bytes(h) bytes at `obs` are changed only by this handle's own
+ * calls that are given that same pointer: td_step, its auto-reset, the reset kernel behind
+ * a step with random_agent = 0, td_reset and td_reset_layouts.  The library may then leave
+ * unwritten any byte it knows to equal what its last write left there: a td_step into the
+ * retained buffer writes, per board, only the 1-KB windows that hold a channel of a class
+ * that may have changed -- the costs, progress and channels 41-44 always; the enemy planes
+ * if the board has an enemy before or after the step; channel 5 after a leak; channels 21-24
+ * when cost_def crosses a tower cost; the tower planes when the tower list changed; the
+ * layout planes only with a new episode.  The buffer then holds exactly what a full write
+ * would have left.  (Read it, copy from it; writing into it breaks the promise.)
+ *   What may be skipped is tracked per handle: a step skips only if its io->obs is the
+ * retained pointer and every board's observation is known to be in it.  That knowledge is
+ * gained by a td_step into the retained buffer (the first one writes every byte), or board
+ * by board by td_reset / td_reset_layouts into it (once every board was reset there), and lost
+ * by every call that changes what some board's observation would be without writing it
+ * there: td_retain_obs itself, td_set_config, td_set_obs_format, td_import_state,
+ * td_opponent, a td_reset / td_reset_layouts with another or a NULL obs, a td_step with
+ * another obs, and any of these calls that fails.  (td_reset / td_reset_layouts into the
+ * retained buffer write the boards they reset whole and keep it; the setters that change
+ * no observation byte -- auto-reset, random_agent, seeds and stream states, the refill
+ * interval, the step kernel and the store policy -- keep it too.)  td_free_device(p) drops
+ * the retention of every live handle whose retained address lies in block p, so an address
+ * a later allocation reuses is never taken for the old buffer; memory from any other
+ * allocator must be un-retained by the caller before it is freed.  The per-element paths
+ * (an obs that is not 16-B / 8-B aligned, L other than 10 / 20 / 30) always write every byte.
+ *   td_retain_obs synchronises the device first.  td_retained_obs: the pointer, or NULL. */
+int td_retain_obs(td_handle* h, const void* obs);
+const void* td_retained_obs(td_handle* h);
+
 int td_abi_version(void);
 /* sizeof(td_step_io) as this library was built (120 on LP64 at ABI 3). */
 int td_step_io_size(void);
