@@ -1,4 +1,4 @@
-// td_board.h -- board rules and observation encoding of the step kernels (td_step.hip):
+// td_board.h -- board rules and observation encoding of the step kernels (td_step_*.h):
 // fail codes, the tower nibble of an LDS cell word, Chebyshev distance, Enemy.damage, the
 // binary / broadcast / distance / enemy channel classes of the (45, L, L) observation, the
 // dry-ring wait and the kernarg-segment read of the step arguments.

@@ -66,7 +66,7 @@ constexpr int kRefillWaves = 1024;
 // step's waves need (8,192 boards, a refill every 4th step: 37.9 us per step at 48 walks, 36.5 at 12, 36.6 at 4,
 // 36.9 at 1; 34.3 without refills, profiles/r02/s21_session.log).
 constexpr int kWalksPerStep = 3;
-// The ring guard (td_step.hip td_refill_kernel, guard = G) runs on the step stream before
+// The ring guard (td_reset.hip td_refill_kernel, guard = G) runs on the step stream before
 // every G-th step and fills every ring below G layouts to G: a board consumes at most one
 // layout per step, so none of the next G steps finds a ring empty, whatever the refill
 // cadence.  G = NSLOT - 1: a ring the side refills keep full only falls below it when a
@@ -307,12 +307,7 @@ int apply_kernel(td_handle* h, int small) {
   // (Write-through beyond the Infinity Cache -- any kernel, TD_OBS_WT=1 -- measured 1.5-1.7x
   // slower steps at 16,384-65,536 boards, profiles/r03/s21.)
   h->obs_wt = h->small && obs_bytes <= 192.0 * 1024 * 1024 ? 1 : 0;
-  const bool has_small = h->L == 10 || h->L == 20 || h->L == 30;
-  const char* k = !has_small || small == 0 ? "td_step_kernel" : small == 1 ? "td_step_kernel_small" : "td_step_kernel_small2";
-  char buf[96];
-  std::snprintf(buf, sizeof buf, "%s%s<%d, %d, %s>", k, f16 ? "_f16" : "", has_small ? h->L : 0, h->mode,
-                h->multi ? "true" : "false");
-  h->kernel_name = buf;
+  h->kernel_name = step_kernel_name(base_args(h));
   return 0;
 }
 
@@ -876,7 +871,7 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   a.obs_skip = retained && h->retained_valid ? 1 : 0;
   ObsGuard guard{h};
   // the refill goes first: it waits for the previous step only, so a board whose ring
-  // is dry in this step can wait for it (td_step.hip step_board) without a cycle
+  // is dry in this step can wait for it (td_step_body.h step_board) without a cycle
   // random_agent=True: layouts are staged ahead by refills on the side streams.
   // random_agent=False: they are drawn in stream order right after the step (below).
   if (h->autoreset && !h->opp_np && h->refill_every > 0 && (h->steps % h->refill_every) == 0 &&

@@ -1,6 +1,9 @@
-// td_kernels.h -- launch interface between the C-ABI (td_capi.hip) and the kernels (td_step.hip).
+// td_kernels.h -- launch interface between the C-ABI (td_capi.hip) and the kernel units
+// (td_step.hip, td_step_f16.hip, td_reset.hip, td_mask.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include <string>
 
 #include "td_common.h"
 #include "../../include/tdstep.h"
@@ -88,15 +91,22 @@ __host__ __device__ inline int xcd_board(int i, int B) {
 }
 
 
+// The step of a.small's kernel, or with reset = true the reset kernel (launch_reset).
 // ev0 / ev1: optional timing events bound to the step kernel's dispatch (td_kernel_timing).
 hipError_t launch_step(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-// The step with a float16 observation (a.obs_f16; called by launch_step; td_step_f16.hip).
-hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-int step_resident_boards_f16(const StepArgs& a, int cus, int waves);
 // Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute
 // units, for the one-wave (td_step_kernel_small) or two-wave (td_step_kernel_small2) build
 // of the observation format a.obs_f16.
 int step_resident_boards(const StepArgs& a, int cus, int waves);
+// The step kernel a.small selects for an aligned observation buffer, as a profiler prints
+// it (td_step_kernel_name): from the same table launch_step launches from (td_step_launch.h).
+std::string step_kernel_name(const StepArgs& a);
+// The same three for a float16 observation (a.obs_f16; called by the above; td_step_f16.hip).
+hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+int step_resident_boards_f16(const StepArgs& a, int cus, int waves);
+std::string step_kernel_name_f16(const StepArgs& a);
+// TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
+hipError_t launch_reset(const StepArgs& a, hipStream_t s);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),
 // drawing their layouts from the shared numpy stream now (same stream, after the step).
 hipError_t launch_autoreset(const StepArgs& a, hipStream_t s);
@@ -104,7 +114,7 @@ hipError_t launch_autoreset(const StepArgs& a, hipStream_t s);
 hipError_t launch_cfg_usage(const StepArgs& a, uint32_t* used, hipStream_t s);
 // Draw staged layouts for every board whose ring has a free slot: a side-stream refill
 // (guard = 0), or the ring guard on the step stream (guard = G: every ring below G
-// layouts filled to G, draws run to the end; td_step.hip td_refill_kernel).
+// layouts filled to G, draws run to the end; td_reset.hip td_refill_kernel).
 hipError_t launch_refill(const StepArgs& a, hipStream_t s, int guard = 0);
 // The built-in opponent (side 0: random_enemy_lv<level>, 1: random_tower_lv<level>)
 // on the boards in a.reset_mask (nullptr = all).

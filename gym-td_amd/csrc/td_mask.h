@@ -1,6 +1,6 @@
 // td_mask.h -- what the next step would answer to one action, decided from the board's
 // present state: the comparisons tower_build / tower_lvup / tower_destruct / summon_cluster
-// make (td_step.hip), in their order, without the step's side effects.  Shared by the mask
+// make (td_step_rules.h), in their order, without the step's side effects.  Shared by the mask
 // kernel (td_mask.hip) and any host code that wants the same verdicts.
 #pragma once
 #include "td_board.h"

@@ -101,7 +101,7 @@ struct MtRef {
   }
 };
 
-// Lazy-twist form used on the device (td_step.hip WaveMt): w[625] = tw, words
+// Lazy-twist form used on the device (td_step_opp.h WaveMt): w[625] = tw, words
 // [tw, 624) of the current block are not yet twisted.  Complete them in place,
 // giving CPython's ``getstate()`` form (624 words + position).
 TD_HD inline void mt_finish_lazy(uint32_t* w) {

@@ -1,5 +1,43 @@
-// td_step_f16.hip -- the step kernels that write a float16 observation (td_set_obs_format),
-// as a compilation unit of their own: td_step.hip with only launch_step_f16 and the
-// kernels it launches (see there).
-#define TD_STEP_F16_UNIT 1
-#include "td_step.hip"
+// td_step_f16.hip -- the step kernels that write a float16 observation (td_set_obs_format):
+// the _f16 variants of td_step.hip's three kernels (see there) with launch_step_f16,
+// step_resident_boards_f16 and step_kernel_name_f16.  A unit of its own, so that the two
+// formats compile beside each other, not one behind the other.
+#include "td_kernels.h"
+#include "td_step_body.h"
+#include "td_step_launch.h"
+
+namespace td {
+
+// The float16 observation (td_set_obs_format): the same step, the writers instantiated
+// for _Float16.  Kernels of their own name, so the float32 kernels keep theirs.
+template <int LT, int MODE, bool SCAN>
+__global__ __launch_bounds__(64) void td_step_kernel_f16(StepArgs a) {
+  step_kernel_body<LT, MODE, SCAN, false, _Float16>(a);
+}
+
+template <int LT, int MODE, bool SCAN>
+__global__ __launch_bounds__(64) TD_SMALL_ATTR void td_step_kernel_small_f16(StepArgs a) {
+  step_kernel_body<LT, MODE, SCAN, true, _Float16>(kargs(a));
+}
+
+#define TD_SMALL2_NAME td_step_kernel_small2_f16
+#define TD_SMALL2_OT _Float16
+#include "td_step_small2.inc"
+#undef TD_SMALL2_NAME
+#undef TD_SMALL2_OT
+
+// This unit's rows of the launch table (td_step_launch.h).
+template <int LT, int MODE, bool SCAN>
+struct F16Kernels {
+  static StepKernel large() { return {td_step_kernel_f16<LT, MODE, SCAN>, 64, "td_step_kernel_f16"}; }
+  static StepKernel small() { return {td_step_kernel_small_f16<LT, MODE, SCAN>, 64, "td_step_kernel_small_f16"}; }
+  static StepKernel small2() { return {td_step_kernel_small2_f16<LT, MODE, SCAN>, 128, "td_step_kernel_small2_f16"}; }
+};
+
+hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  return launch_step_kernel<F16Kernels, _Float16>(a, s, ev0, ev1);
+}
+int step_resident_boards_f16(const StepArgs& a, int cus, int waves) { return step_kernel_resident<F16Kernels>(a, cus, waves); }
+std::string step_kernel_name_f16(const StepArgs& a) { return step_kernel_display_name<F16Kernels>(a); }
+
+}  // namespace td

@@ -1,5 +1,5 @@
-// td_step_small2.inc -- the two-wave step kernel, included by td_step.hip once per
-// observation format with TD_SMALL2_NAME (the kernel) and TD_SMALL2_OT (the output element)
+// td_step_small2.inc -- the two-wave step kernel, included by td_step.hip and td_step_f16.hip,
+// once per observation format, with TD_SMALL2_NAME (the kernel) and TD_SMALL2_OT (the output element)
 // defined.  One text instead of a function template both kernels call: the float32 kernel,
 // the one bench.py measures, stays the kernel it was, instruction for instruction (a shared
 // body function compiled to different code).

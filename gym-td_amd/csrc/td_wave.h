@@ -1,5 +1,5 @@
-// td_wave.h -- wave-level helpers shared by the step and layout kernels (td_step.hip,
-// td_wavegen.h): exact-rounding f64 / f32 intrinsics, ballots and lane broadcasts,
+// td_wave.h -- wave-level helpers shared by the step and layout kernels (td_step_*.h,
+// td_reset.hip, td_wavegen.h): exact-rounding f64 / f32 intrinsics, ballots and lane broadcasts,
 // agent-scope relaxed accesses, the board claim, state stores and the wave sync.
 #pragma once
 #include <hip/hip_runtime.h>

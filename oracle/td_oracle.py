@@ -463,7 +463,7 @@ class Board(object):
             if self.cost_atk < e.cost:
                 real.append(cfg.enemy_types)
             elif self.enemy_cap is not None and len(self.enemies) >= self.enemy_cap:
-                self.refused[0] += 1  # after the cost check, free of charge (td_step.hip summon_cluster)
+                self.refused[0] += 1  # after the cost check, free of charge (td_step_rules.h summon_cluster)
                 real.append(cfg.enemy_types)
             else:
                 self.cost_atk -= e.cost
@@ -495,7 +495,7 @@ class Board(object):
             self.fail_code = FAIL_POS
             return False
         if self.tower_cap is not None and len(self.towers) >= self.tower_cap:
-            self.refused[1] += 1  # after the cost and position checks (td_step.hip tower_build)
+            self.refused[1] += 1  # after the cost and position checks (td_step_rules.h tower_build)
             self.fail_code = FAIL_CAP
             return False
         self.towers.append(tw)

@@ -1,7 +1,7 @@
 // obs_ceiling.hip -- diagnostic: the observation stream of the step kernel with nothing
 // else in the kernel.  One 64-lane workgroup per board, 18,000 B per board (a 10x10
 // observation) back to back, 128-B-aligned 1-KB windows, the store policy of
-// write_obs_lines (td_step.hip): whole lines non-temporal and the two lines a board shares
+// write_obs_lines (td_step_obs.h): whole lines non-temporal and the two lines a board shares
 // with its neighbours plain (edge_wt = 2), or every line write-through (the small batches'
 // obs_wt); block i steps board xcd_board(i) (td_kernels.h) or board i.  The buffer comes
 // from hipMalloc or hipExtMallocWithFlags(hipDeviceMallocContiguous) (td_alloc_device).

@@ -6,7 +6,7 @@ module.
 
 The step kernels keep a board's enemies two per lane -- lane l owns list entries l and
 l + 64 -- and every phase of the step has a branch of its own for the second entry
-(gym-td_amd/csrc/td_step.hip board_step / enemy_stats / store_enemies).  A scenario is a
+(gym-td_amd/csrc td_step_rules.h board_step, td_step_obs.h enemy_stats, td_step_state.h store_enemies).  A scenario is a
 game config, a mode and a seeded policy under which the REFERENCE rules put more than 64
 enemies (up to exactly 128, the device's capacity) or 32 towers (likewise) on a board;
 `Counters` records, from the oracle's own lists, which of those second-half branches a

@@ -1,7 +1,7 @@
 """Boards with 65-128 live enemies and full tower lists, against the oracle, bit for bit.
 
 Lane l of a step wave owns enemies l and l + 64, and every phase of the step has a branch
-of its own for the second one (td_step.hip board_step: the rank sort across the halves, the
+of its own for the second one (td_step_rules.h board_step: the rank sort across the halves, the
 target `m0 ? ctz(m0) : 64 + ctz(m1)`, the shots on lp[1], the compaction offset
 popc(k0) + popc(k1 & lt); enemy_stats: group heads up to index 127 next to the 0xFF
 sentinel; store_enemies and the three kernels' load paths beyond the 16 prefetched slots;

@@ -10,7 +10,7 @@ skipped on both sides).  The two shapes are chosen so that boards carry more tha
 16 live enemies (10x10, an idle defender against a fast attacker: 25-65, asserted as
 more than 48) and more than 16 towers (20x20, a builder defender): the step kernel
 prefetches 16 enemy and 16 tower slots with the header and loads the rest afterwards
-(the large kernel loads exactly the live slots once the header is in; td_step.hip
+(the large kernel loads exactly the live slots once the header is in; td_step_state.h
 prefetch_issue / load_board).  These runs do not pin the upper half of the enemy list
 (lanes hold enemies l and l + 64, board_step): a few boards here go just past 64 enemies
 for a while (enough to trip over a wrong compaction offset there), but nothing below
