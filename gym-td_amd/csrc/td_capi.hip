@@ -86,6 +86,7 @@ struct td_handle {
   int kernel_forced = 0;      // td_set_step_kernel chose the kind (else TD_KERNEL_AUTO: auto_kernel)
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
+  int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
   std::string kernel_name;    // td_step_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
@@ -271,6 +272,7 @@ StepArgs base_args(td_handle* h) {
   a.small = h->small;
   a.obs_wt = h->obs_wt;
   a.obs_f16 = h->obs_fmt == TD_OBS_F16 ? 1 : 0;
+  a.frame_skip = h->frame_skip;
   a.hdr = h->d_hdr; a.en_lp = h->d_en_lp; a.en_mg = h->d_en_mg; a.en_inf = h->d_en_inf;
   a.tw_cd = h->d_tw_cd; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.opp_mt = h->d_opp; a.opp_hot = h->d_hot;
   a.np_mt = h->d_np; a.nxt = h->d_nxt; a.scratch = h->d_scratch; a.scratch_stride = h->scratch_stride;
@@ -307,7 +309,8 @@ int apply_kernel(td_handle* h, int small) {
   // (Write-through beyond the Infinity Cache -- any kernel, TD_OBS_WT=1 -- measured 1.5-1.7x
   // slower steps at 16,384-65,536 boards, profiles/r03/s21.)
   h->obs_wt = h->small && obs_bytes <= 192.0 * 1024 * 1024 ? 1 : 0;
-  h->kernel_name = step_kernel_name(base_args(h));
+  // (while frame skip is on, td_step launches the skip kernel whatever kind is kept here)
+  h->kernel_name = h->frame_skip > 1 ? skip_kernel_name(base_args(h)) : step_kernel_name(base_args(h));
   return 0;
 }
 
@@ -691,6 +694,9 @@ int td_set_autoreset(td_handle* h, int on) {
 // layouts out with explicit resets, clears them).
 int td_set_random_agent(td_handle* h, int random_agent) {
   if (!h) return fail("NULL handle");
+  if (!random_agent && h->frame_skip > 1)
+    return fail("random_agent=False: not supported with frame skip (td_frame_skip() = %d); set td_set_frame_skip(h, 1) first",
+                h->frame_skip);
   HIP_OK(hipDeviceSynchronize());
   h->since_guard = kGuardEvery;
   if (!random_agent && !h->opp_np) {
@@ -888,7 +894,9 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
     e1 = h->tev[2 * (size_t)h->tev_n + 1];
     h->tev_n += 1;
   }
-  HIP_OK(launch_step(a, s, false, e0, e1));
+  // frame skip: one launch of the skip kernel runs the k board steps (td_step_skip.h).  The refill
+  // cadence and the ring guard above count launches: a board consumes at most one layout per launch.
+  HIP_OK(h->frame_skip > 1 ? launch_skip(a, s, e0, e1) : launch_step(a, s, false, e0, e1));
   if (h->autoreset && h->opp_np) HIP_OK(launch_autoreset(a, s));
   h->steps += 1;
   h->since_guard += 1;
@@ -958,6 +966,21 @@ int td_set_obs_format(td_handle* h, int fmt) {
 }
 
 int td_obs_format(td_handle* h) { return h ? h->obs_fmt : fail("NULL handle"); }
+
+// Board steps per td_step.  No board state changes and the retained observation stays
+// known: only the kernel td_step launches, and its name, follow k.
+int td_set_frame_skip(td_handle* h, int k) {
+  if (!h) return fail("NULL handle");
+  if (k < 1 || k > TD_MAX_FRAME_SKIP)
+    return fail("td_set_frame_skip: k = %d outside [1, %d] (TD_MAX_FRAME_SKIP)", k, TD_MAX_FRAME_SKIP);
+  if (k > 1 && h->multi) return fail("td_set_frame_skip: k = %d > 1 is not supported on a multi-action handle", k);
+  if (k > 1 && h->opp_np) return fail("td_set_frame_skip: k = %d > 1 is not supported with random_agent=False", k);
+  HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
+  h->frame_skip = k;
+  return apply_kernel(h, h->small);
+}
+
+int td_frame_skip(td_handle* h) { return h ? h->frame_skip : fail("NULL handle"); }
 
 size_t td_obs_bytes(td_handle* h) {
   return h ? (size_t)h->B * NCH * h->NC * (h->obs_fmt == TD_OBS_F16 ? 2u : 4u) : 0;

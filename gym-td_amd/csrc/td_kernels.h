@@ -54,6 +54,9 @@ struct StepArgs {
   const TdDevCfg* cfg;   // the current constant block (= cfgs + epoch)
   const TdDevCfg* cfgs;  // [NCFG] one block per paramConfig epoch (entities keep their epoch's values)
   int epoch;
+  int frame_skip;  // board steps per launch (td_set_frame_skip), read by the skip kernels only (td_step_skip.h).
+                   // In the 4 bytes of padding behind epoch: no field's kernarg offset moves, the struct
+                   // keeps its size, and every other kernel compiles to the code it was.
   const int64_t* def_act;
   const int64_t* atk_act;
   float* obs;           // _Float16* with obs_f16
@@ -77,7 +80,9 @@ struct StepArgs {
   int obs_skip;  // obs is the retained buffer and holds every board's last observation (td_retain_obs): the
                  // step may leave the windows of clean dirty classes unwritten (write_obs_lines)
 };
-
+static_assert(offsetof(StepArgs, frame_skip) == offsetof(StepArgs, epoch) + 4 && offsetof(StepArgs, def_act) % 8 == 0 &&
+                  offsetof(StepArgs, def_act) == offsetof(StepArgs, epoch) + 8,
+              "frame_skip lies in the padding behind epoch");
 constexpr int NXCD = 8;  // XCDs of an MI355X: block i runs on XCD i % 8
 
 // The XCD-contiguous board map: block i (XCD i % 8, slot i / 8) steps board
@@ -105,6 +110,13 @@ std::string step_kernel_name(const StepArgs& a);
 hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 int step_resident_boards_f16(const StepArgs& a, int cus, int waves);
 std::string step_kernel_name_f16(const StepArgs& a);
+// Frame skip (a.frame_skip > 1): a.frame_skip board steps per board in one launch of the
+// skip kernel of a.L, a.mode and a.obs_f16 (td_step_skip.hip, td_step_skip_f16.hip), and
+// that kernel's name as a profiler prints it.  Discrete actions, random_agent=True only.
+hipError_t launch_skip(const StepArgs& a, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+std::string skip_kernel_name(const StepArgs& a);
+hipError_t launch_skip_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+std::string skip_kernel_name_f16(const StepArgs& a);
 // TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
 hipError_t launch_reset(const StepArgs& a, hipStream_t s);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),

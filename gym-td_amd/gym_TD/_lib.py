@@ -20,6 +20,7 @@ HDR_BYTES = 96
 ABI_VERSION = 3  # include/tdstep.h TD_ABI_VERSION
 STEP_KERNELS = {"auto": 0, "large": 1, "small": 2, "small2": 3}  # enum td_step_kernel_kind
 OBS_F32, OBS_F16 = 0, 1  # enum td_obs_format
+MAX_FRAME_SKIP = 16  # TD_MAX_FRAME_SKIP
 
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -112,6 +113,8 @@ def _load():
         "td_obs_bytes": (ctypes.c_size_t, [c_vp]),
         "td_retain_obs": (ctypes.c_int, [c_vp, c_vp]),
         "td_retained_obs": (c_vp, [c_vp]),
+        "td_set_frame_skip": (ctypes.c_int, [c_vp, ctypes.c_int]),
+        "td_frame_skip": (ctypes.c_int, [c_vp]),
         "td_step_kernel": (ctypes.c_int, [c_vp]),
         "td_step_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_config_epoch": (ctypes.c_int, [c_vp]),

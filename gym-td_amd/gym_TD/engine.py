@@ -158,11 +158,17 @@ class TDEngine(object):
           returns (in-place normalisation, masking) must work on a copy, or construct
           with retain_obs=False.  Ignored with host_io; TD_RETAIN_OBS=0 turns it off
           for every engine.
+    frame_skip: board steps per ``step()`` (td_set_frame_skip), 1 (default) .. 16.  With
+          k > 1 a step is a macro step: the given action, then k - 1 empty actions, in one
+          launch that writes one observation; reward is the sum, done / info those of the
+          last board step run (a board stops at its episode's end), RealAction / FailCode
+          those of the first.  Discrete actions and random_agent=True only.
     """
 
     def __init__(self, map_size, n_boards, mode="def", multi_action=None, difficulty=1, device=None,
                  np_seeds=None, py_seeds=None, autoreset=True, info=True, cfg=None, hp=None, host_io=False,
-                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32, retain_obs=True):
+                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32, retain_obs=True, frame_skip=1):
+        frame_skip = _check_frame_skip(frame_skip)  # (before td_create: no device is touched)
         if obs_dtype not in OBS_FORMATS:  # (before td_create: no device is touched)
             raise ValueError("obs_dtype must be torch.float32 or torch.float16, not %r" % (obs_dtype,))
         if not isinstance(retain_obs, (bool, np.bool_)):
@@ -244,6 +250,13 @@ class TDEngine(object):
             self.seed(np_seeds, py_seeds)
         if step_kernel != "auto":
             self.set_step_kernel(step_kernel)
+        self.frame_skip = 1
+        if frame_skip != 1:
+            try:
+                self.set_frame_skip(frame_skip)
+            except Exception:
+                self.close()
+                raise
         P._live.add(self)
 
     # ------------------------------------------------------------------ setup
@@ -492,6 +505,14 @@ class TDEngine(object):
             raise ValueError("step kernel must be one of %s" % sorted(_lib.STEP_KERNELS))
         _lib.check(_lib.lib.td_set_step_kernel(self._h, _lib.STEP_KERNELS[kind]))
 
+    def set_frame_skip(self, k):
+        """Board steps per step() from the next step on (td_set_frame_skip): 1 .. 16.  No
+        board state changes; refused (TDError) with k > 1 on a multi-action or
+        random_agent=False engine."""
+        k = _check_frame_skip(k)
+        _lib.check(_lib.lib.td_set_frame_skip(self._h, k))
+        self.frame_skip = k
+
     def set_obs_dtype(self, obs_dtype, obs=None):
         """Switch the observation's element between steps (td_set_obs_format): ``obs`` is
         the new buffer (B, 45, L, L) of that dtype, a fresh one if None.  No board state
@@ -595,6 +616,12 @@ class TDEngine(object):
         start = [[int(c) // L, int(c) % L] for c in h["start_cell"][:nr]]
         end = [int(h["end_cell"]) // L, int(h["end_cell"]) % L]
         return m, start, end
+
+
+def _check_frame_skip(k):
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.MAX_FRAME_SKIP:
+        raise ValueError("frame_skip must be an int in [1, %d], not %r" % (_lib.MAX_FRAME_SKIP, k))
+    return int(k)
 
 
 def _as_dev(x, dtype, device):

@@ -102,12 +102,15 @@ class _TDBasic(object):
     ``random_agent=False``: the opponent draws from the env's ``np_random``, the
     stream reset() draws layouts from (TDGymBasic.py:87-89,101-103,118-120,139-191,
     213-287), checked against the oracle's restatement (not pinned by reference runs).
+    ``frame_skip=k`` (an extension, default 1): step(action) runs the action and then k - 1
+    empty actions as one launch (TDEngine's ``frame_skip``) and returns the summed reward,
+    the last observation and the first board step's RealAction / FailCode.
     """
     metadata = {"render.modes": ["human", "rgb_array"], "video.frames_per_second": 50}
     _mode = "def"
 
     def __init__(self, map_size, seed=None, fixed_seed=False, random_agent=True, difficulty=1,
-                 opponent_seed=None, device=None):
+                 opponent_seed=None, device=None, frame_skip=1):
         self.map_size = int(map_size)
         self.observation_space = Box(low=0., high=1., shape=(45, self.map_size, self.map_size), dtype=np.float32)
         self.fixed_seed, self.input_seed, self.random_agent = fixed_seed, seed, random_agent
@@ -115,7 +118,8 @@ class _TDBasic(object):
         self._multi = bool(P.hyper_parameters.allow_multiple_actions)
         self._engine = TDEngine(self.map_size, 1, self._mode, self._multi, difficulty if self._mode != "2p" else 1,
                                 device=device, autoreset=False, info=True, host_io=True,
-                                random_agent=random_agent)
+                                random_agent=random_agent, frame_skip=frame_skip)
+        self.frame_skip = self._engine.frame_skip
         if opponent_seed is not None:
             self._engine.seed(py_seeds=[opponent_seed])
         else:
@@ -323,18 +327,21 @@ class TDVecEnv(object):
     defender's in TD-2p) and ``infos['action_mask_attacker']`` (TD-atk, TD-2p) hold the legal actions
     of the state the step left (TDEngine.action_mask); after reset(), ``action_masks()``.
     ``obs_dtype=torch.float16``: the observation as float16 (TDEngine's ``obs_dtype``).
+    ``frame_skip=k``: every step() is a macro step of k board steps (TDEngine's
+    ``frame_skip``); with ``action_mask=True`` the mask describes the state it left.
     """
 
     def __init__(self, map_size, num_envs, mode="def", difficulty=1, multi_action=None, seed=0, global_offset=0,
                  device=None, info=True, autoreset=True, host_io=False, random_agent=True, action_mask=False,
-                 obs_dtype=torch.float32):
+                 obs_dtype=torch.float32, frame_skip=1):
         self.map_size, self.num_envs, self.mode = int(map_size), int(num_envs), mode
         self.with_action_mask = bool(action_mask)
         self._masks = None
         seeds = np.arange(num_envs, dtype=np.int64) + int(seed) + int(global_offset)
         self.engine = TDEngine(map_size, num_envs, mode, multi_action, difficulty, device=device,
                                np_seeds=seeds, py_seeds=seeds, autoreset=autoreset, info=info, host_io=host_io,
-                               random_agent=random_agent, obs_dtype=obs_dtype)
+                               random_agent=random_agent, obs_dtype=obs_dtype, frame_skip=frame_skip)
+        self.frame_skip = self.engine.frame_skip
         L = self.map_size
         self.observation_space = Box(low=0., high=1., shape=(45, L, L),
                                      dtype=np.float16 if obs_dtype == torch.float16 else np.float32)

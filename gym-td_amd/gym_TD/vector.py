@@ -42,10 +42,11 @@ class VectorEnv(object):
     (every auto-reset draws the env's next layout); the single-env classes support it.
     ``obs_dtype``: ``np.float32`` (default) or ``np.float16`` (or the torch dtypes): the
     observations' element, written in that form by the step kernels.
+    ``frame_skip``: board steps per step() (TDEngine's ``frame_skip``; default 1).
     """
 
     def __init__(self, env_id, num_envs, map_size=None, difficulty=1, seed=None, fixed_seed=False, device=None,
-                 random_agent=True, obs_dtype=np.float32):
+                 random_agent=True, obs_dtype=np.float32, frame_skip=1):
         if fixed_seed:
             raise NotImplementedError("fixed_seed=True: use the single-env classes (gym_TD.envs.TDDefense ...)")
         self.kind, self.map_size = _parse(env_id, map_size)
@@ -63,7 +64,8 @@ class VectorEnv(object):
             obs_dtype = getattr(torch, name)
         self.vec = _envs.TDVecEnv(self.map_size, self.num_envs, self.kind, difficulty=difficulty, seed=self._seed,
                                   device=device, info=True, host_io=True, random_agent=self._random_agent,
-                                  obs_dtype=obs_dtype)
+                                  obs_dtype=obs_dtype, frame_skip=frame_skip)
+        self.frame_skip = self.vec.frame_skip
         self.observation_space = self.vec.observation_space
         self.single_action_space = self.vec.action_space
         self.action_space = self.vec.action_space
@@ -75,10 +77,10 @@ class VectorEnv(object):
         def make():
             if self.kind == "2p":
                 return _envs.TDMulti(self.map_size, seed=self._seed + i, opponent_seed=self._seed + i,
-                                     random_agent=self._random_agent)
+                                     random_agent=self._random_agent, frame_skip=self.frame_skip)
             cls = _envs.TDDefense if self.kind == "def" else _envs.TDAttack
             return cls(self.map_size, difficulty=self._difficulty, seed=self._seed + i, opponent_seed=self._seed + i,
-                       random_agent=self._random_agent)
+                       random_agent=self._random_agent, frame_skip=self.frame_skip)
         return make
 
     def seed(self, seeds=None):

@@ -171,6 +171,36 @@ size_t td_obs_bytes(td_handle* h);
 int td_retain_obs(td_handle* h, const void* obs);
 const void* td_retained_obs(td_handle* h);
 
+/* Frame skip (an extension; off by default: k = 1, and nothing changes).  With k > 1 one
+ * td_step is a macro step: every board runs up to k board steps ("sub-steps") in one launch
+ * and ONE observation is written -- the observation's cost per board step becomes 1 / k.
+ *   Sub-step 0 takes the caller's actions exactly as a step does (FLAG_BAD_ACTION included);
+ * sub-steps 1 .. k-1 take the empty action for every side the caller controls (defender:
+ * 6 L^2, attacker: all 4s), as the reference's trainer steps when no move is allowed.  The
+ * built-in opponents act in every sub-step on the board's own stream and the cool-downs
+ * decrement every sub-step, as in k separate steps.  A board stops after the sub-step that
+ * finishes its episode; with auto-reset its new episode starts there (at most one staged
+ * layout per board per launch).
+ *   Outputs: reward = r0, then the f64 sum left to right over the executed sub-steps
+ * (TD-atk: each already negated); done, win, allow_next, cooldowns, ep_return, ep_len = what
+ * the last executed sub-step would have written (ep_len and td_episode_records keep
+ * counting board steps); real_def / fail_def / real_atk / fail_atk = sub-step 0's, the only
+ * one that carried an action; board flags are OR-ed; obs = the state after the last executed
+ * sub-step (after an auto-reset: the new episode's first observation), written once in the
+ * handle's format and store policy.  With td_retain_obs "before" is the board as loaded at
+ * the start of the macro step.  On a board where no sub-step finishes an episode, state,
+ * both RNG streams and every output equal those of k steps (action, empty, ..., empty).
+ *   td_set_frame_skip may be called between any two steps (it synchronises the device
+ * first) and changes no board state.  Refused (< 0, td_last_error, nothing changed):
+ * k outside 1 .. TD_MAX_FRAME_SKIP; k > 1 on a multi-action handle; k > 1 with
+ * random_agent = 0 -- and td_set_random_agent(h, 0) while k > 1.  While k > 1 td_step
+ * launches "td_skip_kernel<L, mode>" / "td_skip_kernel_f16<L, mode>" (td_step_kernel_name)
+ * whatever kind td_set_step_kernel chose; that choice is kept for k = 1.  The refill cadence
+ * and the ring guard count launches, and td_kernel_timing times the launch. */
+#define TD_MAX_FRAME_SKIP 16
+int td_set_frame_skip(td_handle* h, int k);
+int td_frame_skip(td_handle* h);
+
 int td_abi_version(void);
 /* sizeof(td_step_io) as this library was built (120 on LP64 at ABI 3). */
 int td_step_io_size(void);
