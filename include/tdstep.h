@@ -47,10 +47,21 @@ extern "C" {
 
 enum td_mode { TD_MODE_DEF = 0, TD_MODE_ATK = 1, TD_MODE_2P = 2 };
 
+/* TD_FLAG_BAD_ACTION, the rule (the reference asserts on such input; this is the device's own,
+ * pinned by tests/test_gpu_bad_action.py).  Actions are int64 and all 64 bits count.
+ *   discrete defender   an action outside 0 .. 6 L^2 becomes 6 L^2, the empty action:
+ *                       real_def = 6 L^2, fail_def = 0
+ *   attacker            each entry outside 0 .. 4 becomes 4 ("none") -- that entry, not its
+ *                       cluster; real_atk shows 4 there
+ *   multi-action flags  each flag outside 0 .. 2 counts as 0; its real-action entry is 0
+ * The board's flag word gains TD_FLAG_BAD_ACTION in that step, whether or not the side is
+ * cooling down, and the step then runs exactly as with the sanitised action.  No other board
+ * is touched.  Like every flag it survives an auto-reset and is cleared by an explicit reset
+ * (td_reset / td_reset_layouts) of that board. */
 enum td_board_flag {
   TD_FLAG_EN_OVERFLOW = 1, /* more than 128 live enemies: summon refused */
   TD_FLAG_TW_OVERFLOW = 2, /* more than 32 towers: build refused */
-  TD_FLAG_BAD_ACTION = 4,  /* action outside the action space (the reference asserts) */
+  TD_FLAG_BAD_ACTION = 4,  /* an action value outside the action space: sanitised, see above */
   TD_FLAG_NO_LAYOUT = 8,   /* auto-reset found no staged layout */
   TD_FLAG_BAD_MOVE = 16,   /* an enemy walked off the board (corrupt layout) */
   TD_FLAG_CLAIM_TIMEOUT = 32 /* a wait for the board's refill claim gave up after 1 s: the ring

@@ -59,6 +59,22 @@ def test_scenario_reaches_its_branches(refs, name):
     assert ref.running >= ref.scn.B - 1
 
 
+@pytest.mark.parametrize("name,k", U.SKIP_CASES)
+def test_scenario_reaches_its_branches_at_frame_skip(name, k):
+    """The same floors with the scenario run as steps // k macro steps at frame skip k (the
+    policy once per macro step, crowdutil.Reference(scn, k)): what
+    tests/test_gpu_frame_skip_crowded.py compares the td_skip_kernel family on.  Examples of
+    what the oracle gave at k = 2: full-atk 20 board-steps on 128 enemies, 13 heads at index
+    127 and 105 kills in the upper half; overflow-atk 2,345 refused summons on 7 of 8 boards;
+    towers-def 772 board-steps on 32 towers, 216 refused builds, 47 destructs on a full list;
+    overflow-2p refusals on exactly 4 of 8 boards."""
+    ref = U.Reference(U.BY_NAME[name], k)
+    ref.steps = None
+    print(name, k, ref.counters, ref.refused)
+    U.check_scenario(ref)
+    assert ref.running >= ref.scn.B - 1
+
+
 def test_uncapped_scenarios_cover_the_upper_half(refs):
     """Over the scenarios that need no cap on the oracle: every second-half branch of the
     step ran, many times over for the common ones."""

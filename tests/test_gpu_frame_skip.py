@@ -7,6 +7,7 @@ the next layout draw that succeeds, rewards summed left to right in f64.  Everyt
 compared bit for bit.  tests/test_frame_skip_ref.py shows on the CPU that the recipe ends at
 least 5 episodes at every sub-step position, so a pass here means the early-stop branch ran
 at each of them."""
+import copy
 import functools
 
 import numpy as np
@@ -114,6 +115,8 @@ def _compare(eng, outs, where, f16=False):
         t = getattr(eng, n)
         host[n] = None if t is None else t.cpu().numpy()
     for b, o in enumerate(outs):
+        if o is None:  # (a board the caller compares by itself)
+            continue
         w = (where, b, o["ran"])
         want = np.asarray(o["obs"], dtype=np.float32)
         want = want.astype(np.float16) if f16 else want
@@ -162,8 +165,10 @@ def _run(tr, f16=False, **kw):
 # ------------------------------------------------------------------ 1 parity
 @pytest.mark.parametrize("mode,k", S.RECIPE_CASES)
 def test_parity_with_the_reference_recipe(mode, k):
-    tr = _trace_def4() if (mode, k) == ("def", 4) else Trace(mode, k)
-    assert (tr.ends() >= 5).all(), tr.ends()  # (tests/test_frame_skip_ref.py, on the C oracle alone)
+    tr = _trace_def4() if (mode, k) == ("def", 4) else Trace(mode, k, steps=S.recipe_steps(mode, k))
+    S.check_ends(mode, k, tr.ends())  # (tests/test_frame_skip_ref.py, on the C oracle alone)
+    if mode == "def" or k == 3:
+        assert (tr.ends() >= 5).all(), tr.ends()
     _run(tr)
 
 
@@ -365,6 +370,115 @@ def test_step_limit_end():
         assert (eng.flags() == 0).all()
     finally:
         eng.close()
+
+
+# ------------------------------------------------------------------ 8b td_set_config between macro steps
+@pytest.mark.parametrize("autoreset", [False, True])
+def test_set_config_between_macro_steps(autoreset):
+    """A new config before every macro step of 3 (skiputil.ConfigTrace): the enemies and towers
+    created in sub-steps 1 and 2 capture the launch's config epoch as those of sub-step 0 do,
+    and with auto-reset an episode that ends inside a macro step starts the next one under
+    that launch's config.  The state digest carries each entity's captured values."""
+    from gym_TD import params as P
+    tr = S.ConfigTrace(autoreset)
+    tr.check()  # (tests/test_frame_skip_ref.py, without a GPU)
+    eng = TDEngine(tr.L, len(tr.seeds), "def", False, 1, np_seeds=tr.seeds, py_seeds=tr.seeds, autoreset=autoreset,
+                   cfg=tr.cfg(0, copy.deepcopy(P.config)), frame_skip=tr.k)
+    try:
+        _, failed = eng.reset()
+        assert not failed
+        ob = eng.obs.cpu().numpy()
+        for b, w in enumerate(tr.first):
+            assert np.array_equal(_bits(ob[b]), _bits(w)), ("first obs", b)
+        for i, (acts, outs) in enumerate(zip(tr.acts, tr.outs)):
+            eng.set_config(tr.cfg(i + 1, copy.deepcopy(P.config)))
+            eng.step(def_act=torch.from_numpy(acts))
+            ob, rw, dn = eng.obs.cpu().numpy(), eng.reward.cpu().numpy(), eng.done.cpu().numpy()
+            real, fail = eng.real_def.cpu().numpy(), eng.fail_def.cpu().numpy()
+            st = eng.export_state()
+            for b, o in enumerate(outs):
+                if o is None:  # (finished in an earlier macro step, no auto-reset)
+                    continue
+                w = (autoreset, i, b, o["ran"])
+                assert canon.fhex(rw[b]) == canon.fhex(o["reward"]) and bool(dn[b]) == o["done"], w
+                assert canon.state_digest(eng.board_state(b, st)) == o["digest"], w
+                assert np.array_equal(_bits(ob[b]), _bits(np.asarray(o["obs"], dtype=np.float32))), w
+                assert int(real[b]) == o["real_def"] and int(fail[b]) == o["fail_def"], w
+        assert (eng.flags() == 0).all()
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ 8c boards never reset
+NEVER_K, NEVER_B, NEVER_STEPS = 4, 32, 6
+FLAG_NO_LAYOUT = 8  # include/tdstep.h td_board_flag
+
+
+@pytest.mark.parametrize("L,dtype,garbage", [(L, dt, False) for L in (10, 20) for dt in (torch.float32, torch.float16)]
+                         + [(10, torch.float32, True), (20, torch.float32, True)])
+def test_boards_never_reset(L, dtype, garbage):
+    """skip_board's own copy of the "never reset" branch: 32 boards with every seed of the
+    road table whose first draw fails (L = 10: 8 of them; the table has none at L = 20) and two
+    boards the caller left out of reset().  At frame skip 4 such a board shows, every macro step,
+    an all-zero observation, done 1, win -1, reward +0.0, nothing allowed, the empty action
+    back, flag word exactly TD_FLAG_NO_LAYOUT and the state the reset left; the healthy boards
+    beside it are the reference's.  garbage: the observation buffer holds 0xA5 before the
+    reset, with retention on -- the windows of those boards are written, not skipped."""
+    import goldens as G
+    rows = G.load_roadgen()[str(L)]
+    err = sorted(int(s) for s in rows if "err" in rows[s])[:8]
+    good = sorted(int(s) for s in rows if "err" not in rows[s])[:NEVER_B - len(err)]
+    seeds = sorted(err + good)
+    left_out = [3, 17]
+    assert all(seeds[b] in good for b in left_out) and (len(err) == 8 or L != 10)
+    never = sorted([b for b, s in enumerate(seeds) if s in err] + left_out)
+    f16 = dtype == torch.float16
+    cfg = S.recipe_cfg()
+    refs = [None if b in never else S.Ref(L, "def", s, cfg) for b, s in enumerate(seeds)]
+    eng = TDEngine(L, NEVER_B, "def", False, 1, np_seeds=seeds, py_seeds=seeds, autoreset=True, cfg=cfg,
+                   obs_dtype=dtype, retain_obs=True, frame_skip=NEVER_K)
+    try:
+        assert eng.retain_obs == _retain_enabled()
+        if garbage:
+            eng.obs.view(torch.uint8).fill_(0xA5)
+        mask = np.ones(NEVER_B, dtype=np.uint8)
+        mask[left_out] = 0
+        _, failed = eng.reset(mask)
+        assert sorted(failed) == [b for b, s in enumerate(seeds) if s in err], (failed, err)
+        st0 = eng.export_state()
+        assert (st0["hdr"]["num_roads"][never] == 0).all() and (st0["hdr"]["flags"] == 0).all()
+        if garbage:
+            assert bool((eng.obs[never].view(torch.uint8) == 0xA5).all())
+        rng = np.random.RandomState(4)
+        empty = 6 * L * L
+        for i in range(NEVER_STEPS):
+            acts = S.draw_actions(rng, "def", NEVER_B, L)
+            outs = [None if r is None else r.macro(NEVER_K, *S.act_of(acts, b)) for b, r in enumerate(refs)]
+            _step(eng, acts)
+            _compare(eng, outs, ("never", L, i), f16)
+            assert not bool(eng.obs[never].view(torch.uint8).any()), i  # every byte zero
+            host = {n: getattr(eng, n).cpu().numpy()[never] for n in
+                    ("reward", "done", "win", "allow_next", "cooldowns", "real_def", "fail_def", "ep_return", "ep_len")}
+            assert (host["reward"].view(np.uint64) == 0).all() and (host["ep_return"].view(np.uint64) == 0).all(), i
+            assert (host["done"] == 1).all() and (host["win"] == -1).all(), i
+            for n in ("allow_next", "cooldowns", "fail_def", "ep_len"):
+                assert (host[n] == 0).all(), (i, n)
+            assert (host["real_def"] == empty).all(), i
+            flags = eng.flags()
+            assert (flags[never] == FLAG_NO_LAYOUT).all() and flags.sum() == FLAG_NO_LAYOUT * len(never), (i, flags.tolist())
+            st = eng.export_state()
+            for name in st0:
+                if name == "hdr":
+                    for f in st0["hdr"].dtype.names:
+                        if f != "flags":
+                            assert np.array_equal(st["hdr"][f][never], st0["hdr"][f][never]), (i, f)
+                else:
+                    assert np.array_equal(st[name][never], st0[name][never]), (i, name)
+    finally:
+        eng.close()
+        for r in refs:
+            if r is not None:
+                r.close()
 
 
 # ------------------------------------------------------------------ 9 refusals
