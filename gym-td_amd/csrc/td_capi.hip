@@ -823,6 +823,14 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
   for (int i = 0; i < n; ++i)
     if (boards[i] < 0 || boards[i] >= h->B || recs[(size_t)i * h->lw] != TD_LAYOUT_MAGIC)
       return fail("td_reset_layouts: bad board id or layout record %d", i);
+  // the step kernels take num_roads and max dist on trust: the channel-9 table has
+  // MAX_ROAD_CELLS entries, indexed by a cell's distance <= max dist
+  for (int i = 0; i < n; ++i) {
+    const uint32_t* r = recs + (size_t)i * h->lw;
+    if (r[1] < 1 || r[1] > 3 || r[3] > (uint32_t)(MAX_ROAD_CELLS - 1))
+      return fail("td_reset_layouts: layout record %d has num_roads %u / max dist %u (must be 1..3 / 0..%d: "
+                  "a road has at most %d cells)", i, r[1], r[3], MAX_ROAD_CELLS - 1, MAX_ROAD_CELLS);
+  }
   HIP_OK(hipDeviceSynchronize());
   const bool mine = n > 0 && obs_reset_into(h, obs);
   ObsGuard guard{h};
@@ -1160,6 +1168,9 @@ int td_import_state(td_handle* h, int b0, int count, const void* host_src) {
                   x.max_base_LP);
     if (x.n_en < 0 || x.n_en > ECAP || x.n_tw < 0 || x.n_tw > TCAP)
       return fail("td_import_state: board %d: %d enemies / %d towers exceed the capacity", b0 + i, x.n_en, x.n_tw);
+    if (x.maxdist < 0 || x.maxdist > MAX_ROAD_CELLS - 1)
+      return fail("td_import_state: board %d: max dist %d (must be 0..%d: a road has at most %d cells)", b0 + i,
+                  x.maxdist, MAX_ROAD_CELLS - 1, MAX_ROAD_CELLS);
   }
   obs_touch(h);
   return state_copy(h, b0, count, const_cast<void*>(host_src), false);

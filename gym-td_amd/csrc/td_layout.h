@@ -317,17 +317,30 @@ struct RoadGen {
 
 // Build a layout record from explicit road cell lists (road i = cells[off[i] .. off[i+1])),
 // exactly as TDBoard.__init__ fills its map planes (TDBoard.py:31-59).
+//
+// The layout rule (include/tdstep.h): a road is a simple 4-connected path of 2..MAX_ROAD_CELLS
+// cells, and every road leads into road 0's last cell.  Checked here: at most MAX_ROAD_CELLS
+// cells, no cell twice, every cell on the board.  The step kernels normalise the
+// distance plane through a table of MAX_ROAD_CELLS entries indexed by the cell's distance
+// (Smem::d9), so a longer road is refused here; create_road_v2 draws at most 2L - 1 <= 63
+// cells.  A road that names a cell twice is refused too: the second exit's direction
+// overwrites the first, so the loop can never be walked, and the reference (which writes
+// map[4] from the end backwards) keeps the other visit's distance.  Any refusal leaves
+// rec[0] = 0, which td_reset_layouts does not take for a record.
+constexpr int MAX_ROAD_CELLS = 64;
+
 TD_HD inline int layout_from_roads(int L, int num_roads, const int32_t* cells, const int32_t* off, uint32_t* rec) {
+  rec[0] = 0;
   if (L < 2 || L > MAX_L || num_roads < 1 || num_roads > 3) return ROAD_ERR_ARGS;
   for (int i = 0; i < L * L; ++i) rec[LAYOUT_HDR + i] = 0;
   uint32_t* cw = rec + LAYOUT_HDR;
-  int maxdist = 0;
   for (int ri = 0; ri < num_roads; ++ri) {
     int a = off[ri], b = off[ri + 1], prev = -1;
-    if (b <= a) return ROAD_ERR_ARGS;
+    if (b <= a || b - a > MAX_ROAD_CELLS) return ROAD_ERR_ARGS;
     for (int k = a; k < b; ++k) {
       int p = cells[k];
       if (p < 0 || p >= L * L) return ROAD_ERR_ARGS;
+      if (cw[p] & (1u << (1 + ri))) return ROAD_ERR_ARGS;  // this road has been here already
       uint32_t w = cw[p] | 1u | (1u << (1 + ri));
       w = (w & 0x00ffffffu) | (1u << 24);
       int dist = b - 1 - k;
@@ -338,9 +351,15 @@ TD_HD inline int layout_from_roads(int L, int num_roads, const int32_t* cells, c
         uint32_t dir = dr == 0 ? (dc == 1 ? 0u : 1u) : (dr == 1 ? 2u : 3u);
         cw[prev] = (cw[prev] & ~(3u << 8)) | (dir << 8);
       }
-      if (dist > maxdist) maxdist = dist;
       prev = p;
     }
+  }
+  // np.max(map[4]) of the finished plane (TDBoard.py:121-122): a later road may have
+  // overwritten the farthest cell of an earlier one with a smaller distance
+  int maxdist = 0;
+  for (int i = 0; i < L * L; ++i) {
+    const int dist = (int)((cw[i] >> 16) & 0xffu);
+    if (dist > maxdist) maxdist = dist;
   }
   for (int ri = 0; ri < num_roads; ++ri) cw[cells[off[ri]]] |= 1u << (5 + ri);
   int endc = cells[off[1] - 1];

@@ -57,13 +57,21 @@ enum td_mode { TD_MODE_DEF = 0, TD_MODE_ATK = 1, TD_MODE_2P = 2 };
  * The board's flag word gains TD_FLAG_BAD_ACTION in that step, whether or not the side is
  * cooling down, and the step then runs exactly as with the sanitised action.  No other board
  * is touched.  Like every flag it survives an auto-reset and is cleared by an explicit reset
- * (td_reset / td_reset_layouts) of that board. */
+ * (td_reset / td_reset_layouts) of that board.
+ *
+ * TD_FLAG_BAD_MOVE: a layout whose road dead-ends away from the end cell (against the layout
+ * rule at td_layout_from_roads) sends an enemy towards a position outside the board.  The
+ * step tests the position before it forms a cell index: the move is not made -- the enemy
+ * keeps its cell, with the margin already reduced by 1, and moves no further in that step --
+ * and the board's flag word gains TD_FLAG_BAD_MOVE in that step.  (The reference indexes its
+ * map with the position: an IndexError, or a wrap to the other edge.)  No other board is
+ * touched; td_reset / td_reset_layouts of that board clear the flag. */
 enum td_board_flag {
   TD_FLAG_EN_OVERFLOW = 1, /* more than 128 live enemies: summon refused */
   TD_FLAG_TW_OVERFLOW = 2, /* more than 32 towers: build refused */
   TD_FLAG_BAD_ACTION = 4,  /* an action value outside the action space: sanitised, see above */
   TD_FLAG_NO_LAYOUT = 8,   /* auto-reset found no staged layout */
-  TD_FLAG_BAD_MOVE = 16,   /* an enemy walked off the board (corrupt layout) */
+  TD_FLAG_BAD_MOVE = 16,   /* an enemy's move would leave the board (a dead-end road): not made, see above */
   TD_FLAG_CLAIM_TIMEOUT = 32 /* a wait for the board's refill claim gave up after 1 s: the ring
                                 guard left its ring short, or its episode end found no layout
                                 (then TD_FLAG_NO_LAYOUT too); see td_guard_timeouts */
@@ -286,7 +294,12 @@ int td_reset(td_handle* h, const uint8_t* host_mask, float* obs, void* stream);
 /* Boards whose road generation failed in the last td_reset (ids into boards[0..cap)); returns the count. */
 int td_last_reset_failures(td_handle* h, int32_t* boards, int cap);
 
-/* Reset from explicit layout records (td_layout_words(L) uint32 each, host memory). */
+/* Reset from explicit layout records (td_layout_words(L) uint32 each, host memory), as
+ * td_layout_from_roads / td_layout_generate make them.  A record without the magic word, with
+ * num_roads (word 1) outside 1 .. 3 or with max dist (word 3) above 63 -- the step kernels'
+ * distance table has 64 entries -- is refused (< 0, td_last_error) before anything is copied
+ * or launched: no board, flag or retained observation changes.  The cell words of a record
+ * are taken as they are. */
 int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, int n, float* obs, void* stream);
 
 /* One env step for all boards (asynchronous on `stream`).  Buffers need only their
@@ -403,7 +416,19 @@ int td_episode_records(td_handle* h, td_episode_record* dev_out, void* stream);
  * cool-down check and update.  Synchronous. */
 int td_opponent(td_handle* h, int side, int level, const uint8_t* host_mask, void* stream);
 
-/* Layout records. */
+/* Layout records.
+ * td_layout_from_roads: road i is cells[offsets[i] .. offsets[i + 1]) (row * L + col, start
+ * first), stamped in order as TDBoard.__init__ stamps its map planes; a later road overwrites
+ * the direction and distance of the cells it shares with an earlier one, and max dist is the
+ * maximum of the finished distance plane (TDBoard.py:121-122).
+ * The layout rule: every road is a simple 4-connected path of 2 .. 64 cells, and every road
+ * leads into road 0's last cell (the end cell).  Returns non-zero, with rec[0] = 0 (not a
+ * record), for num_roads outside 1 .. 3, an empty road, a cell outside the board, a road of
+ * more than 64 cells (the step kernels normalise the distance plane through a 64-entry
+ * table; create_road_v2 draws at most 2 L - 1 <= 63 cells) and a road that names a cell twice
+ * (such a loop can never be walked: the second exit's direction overwrites the first).
+ * Connectivity and the common end are the caller's: a road that dead-ends elsewhere is stepped
+ * under the TD_FLAG_BAD_MOVE rule (td_board_flag). */
 int td_layout_words(int map_size);
 int td_layout_from_roads(int map_size, int num_roads, const int32_t* cells, const int32_t* offsets, uint32_t* rec);
 /* TDGymBasic.reset's draws on one numpy-legacy stream: num_roads = randint(1, 4),
@@ -419,7 +444,10 @@ int td_layout_generate(uint32_t* np_state625, int map_size, int max_attempts, ui
  *   lazy-twist boundary -- words [w[625], 624) still hold the previous block).  Synchronous.
  *   The board's numpy layout stream is not part of the record (it belongs to the stream of
  *   layouts, staged ahead under auto-reset): save / restore it with td_get_np_state /
- *   td_set_np_state -- with random_agent=False it is also the built-in opponent's stream. */
+ *   td_set_np_state -- with random_agent=False it is also the built-in opponent's stream.
+ *   td_import_state checks the header of every board that has a layout (format, captured
+ *   max_cost / max_base_LP, list counts, max dist in 0 .. 63) before it copies anything; a
+ *   refused record leaves nothing imported. */
 size_t td_state_bytes(td_handle* h, int count);
 int td_export_state(td_handle* h, int b0, int count, void* host_dst);
 int td_import_state(td_handle* h, int b0, int count, const void* host_src);

@@ -388,12 +388,21 @@ class Board(object):
     into a full enemy list is refused like one the attacker cannot pay for, a build on a
     full tower list fails with FAIL_CAP.  ``refused`` ([summons, builds], shared with the
     Env so that it outlives a reset) counts those refusals: a board with a non-zero count
-    is one the device flags TD_FLAG_EN_OVERFLOW / TD_FLAG_TW_OVERFLOW."""
+    is one the device flags TD_FLAG_EN_OVERFLOW / TD_FLAG_TW_OVERFLOW.
 
-    def __init__(self, L, num_roads, rng, cfg, hp, roads=None, enemy_cap=None, tower_cap=None, refused=None):
+    ``stay_on_bad_move`` (default False: the reference's rules exactly, which index the map
+    with whatever position comes out) restates the device's guard (td_step_rules.h march): a
+    move that would leave the board is not made -- the enemy keeps its cell, with the margin
+    already reduced by 1, and moves no further in that step -- and ``bad_move`` is set, as
+    the device sets TD_FLAG_BAD_MOVE.  Only a road that dead-ends away from the end cell
+    can cause one."""
+
+    def __init__(self, L, num_roads, rng, cfg, hp, roads=None, enemy_cap=None, tower_cap=None, refused=None,
+                 stay_on_bad_move=False):
         self.L, self.cfg, self.hp = L, cfg, hp
         self.enemy_cap, self.tower_cap = enemy_cap, tower_cap
         self.refused = [0, 0] if refused is None else refused
+        self.stay_on_bad_move, self.bad_move = stay_on_bad_move, False
         if roads is None:
             roads = create_road(rng, L, num_roads)
         self.roads = roads
@@ -572,6 +581,9 @@ class Board(object):
                 e.margin -= 1.
                 d = self.map[5, e.loc[0], e.loc[1]]
                 p = [e.loc[0] + move[d][0], e.loc[1] + move[d][1]]
+                if self.stay_on_bad_move and not self.is_valid_pos(p):
+                    self.bad_move = True
+                    break
                 e.loc, e.dist = p, int(self.map[4, p[0], p[1]])
                 if p[0] == self.end[0] and p[1] == self.end[1]:
                     if self.base_LP is not None and self.base_LP > 0:

@@ -84,7 +84,7 @@ def _assert_equals_reference(eng, m, cfg, hp, where):
 # ------------------------------------------------- 1 + 2: the reference, and the step as judge
 @pytest.mark.parametrize("mode,multi,L,B", [
     ("def", False, 10, 256), ("def", True, 10, 64), ("atk", False, 10, 64), ("2p", False, 20, 32),
-    ("2p", True, 20, 32), ("def", False, 30, 16), ("def", False, 7, 32)])
+    ("2p", True, 20, 32), ("def", False, 30, 16), ("def", False, 7, 32), ("def", False, 32, 8)])
 def test_kernel_equals_reference_and_step_executes(mode, multi, L, B):
     """120 steps of the mask policy, auto-reset on, episodes of 60 steps; the kernel's masks and
     codes against the numpy reference for every board at every 10th step, every chosen action

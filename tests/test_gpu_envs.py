@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import goldens as G
+import steputil
 from oracle import canon, policies
 from oracle import td_oracle as O
 
@@ -42,10 +43,6 @@ def _first_ok_seeds(L, n, start, mode, multi, difficulty, cfg=None, random_agent
     return seeds, envs
 
 
-def _fc_list(row):
-    return [int(v) for v in row if v >= 0]
-
-
 _MODE_CASES = [
     (10, 24, "atk", False, 0, 150, True),
     (10, 24, "atk", False, 1, 150, True),
@@ -66,6 +63,11 @@ _MODE_CASES = [
     (10, 24, "atk", False, 1, 150, False),
     (20, 12, "atk", False, 2, 100, False),
     (30, 6, "def", False, 1, 80, False),
+    # the ends of the size range: 961 cells (odd: the per-element observation path) and 1024, the
+    # whole of Smem<1024>, where generated roads reach 63 cells
+    (31, 4, "def", False, 1, 60, True),
+    (32, 4, "2p", False, 1, 60, True),
+    (32, 4, "atk", False, 2, 60, True),
 ]
 
 
@@ -94,56 +96,13 @@ def test_batched_modes_vs_oracle(L, B, mode, multi, difficulty, steps, random_ag
                 aa = np.stack([policies.atk(rng) for _ in range(B)]).astype(np.int64)
             eng.step(def_act=None if da is None else torch.from_numpy(da),
                      atk_act=None if aa is None else torch.from_numpy(aa))
-            ob, rw, dn = eng.obs.cpu().numpy(), eng.reward.cpu().numpy(), eng.done.cpu().numpy()
-            win, an = eng.win.cpu().numpy(), eng.allow_next.cpu().numpy()
-            cdn = eng.cooldowns.cpu().numpy()
-            assert ((an & 0xFC) == 0).all()  # AllowNextMove bits only (ABI 2: cool-downs have their own output)
-            rd = eng.real_def.cpu().numpy() if eng.real_def is not None else None
-            fd = eng.fail_def.cpu().numpy() if eng.fail_def is not None else None
-            ra = eng.real_atk.cpu().numpy() if eng.real_atk is not None else None
-            fa = eng.fail_atk.cpu().numpy() if eng.fail_atk is not None else None
-            st = eng.export_state()
+            out = steputil.outputs(eng)
             for b, o in enumerate(orc):
                 if o._board.done():
                     continue  # finished in an earlier step (no auto-reset here)
                 d_b = None if da is None else (da[b] if multi else int(da[b]))
-                wo, wr, wd, info = o.step(d_b, None if aa is None else aa[b])
-                tag = (mode, multi, difficulty, k, b)
-                assert canon.fhex(rw[b]) == canon.fhex(wr), tag
-                assert bool(dn[b]) == wd, tag
-                assert canon.state_digest(eng.board_state(b, st)) == canon.state_digest(canon.oracle_state(o)), tag
-                assert np.array_equal(ob[b], wo), (tag, np.argwhere(ob[b] != wo)[:5].tolist())
-                w = info["Win"]
-                if isinstance(w, dict):
-                    w = w["Defender"] if mode != "atk" else w["Attacker"]
-                assert (int(win[b]) if win[b] >= 0 else None) == (None if w is None else int(w)), tag
-                assert (int(cdn[b]) & 15, int(cdn[b]) >> 4) == (min(o.attacker_cd, 15), min(o.defender_cd, 15)), tag
-                anm = info["AllowNextMove"]
-                if mode == "2p":
-                    assert bool(an[b] & 1) == anm["Attacker"] and bool(an[b] & 2) == anm["Defender"], tag
-                elif mode == "atk":
-                    assert bool(an[b] & 1) == anm, tag
-                else:
-                    assert bool(an[b] & 2) == anm, tag
-                real, fc = info["RealAction"], info["FailCode"]
-                if mode == "def":
-                    if multi:
-                        assert np.array_equal(rd[b], real), tag
-                    else:
-                        assert int(rd[b]) == int(real) and int(fd[b]) == int(fc), tag
-                elif mode == "atk":
-                    assert np.array_equal(ra[b], real), tag
-                    assert _fc_list(fa[b]) == list(fc), tag
-                else:
-                    if multi:
-                        assert np.array_equal(ra[b], real["Attacker"]) and np.array_equal(rd[b], real["Defender"]), tag
-                    else:
-                        if isinstance(real, dict):  # no defender success this step
-                            assert np.array_equal(ra[b], real["Attacker"]), tag
-                            assert int(rd[b]) == L * L * 6, tag
-                        else:  # TDMulti.py:257: the defender action replaced the dict
-                            assert int(rd[b]) == int(real), tag
-                        assert _fc_list(fa[b]) == fc["Attacker"] and int(fd[b]) == fc["Defender"], tag
+                stepped = o.step(d_b, None if aa is None else aa[b])
+                steputil.check_board(eng, out, b, o, stepped, mode, multi, (mode, multi, difficulty, k, b))
         assert (eng.flags() == 0).all()
     finally:
         eng.close()

@@ -15,6 +15,10 @@ first step one does:
     L = 10 def, 96 steps: 5 / 44        L = 20 2p multi-action, 160 steps: 26 / 76
     L = 30 def, 200 steps: 21 / 108     L = 12 2p discrete, 96 steps: 8
     L = 11 def, 64 steps: 4             L = 9 atk, 64 steps: 1
+    L = 32 def, 160 steps: 10 / 119     L = 31 atk, 160 steps: 3 / 135
+At L = 31 / 32 an enemy needs over a hundred steps to walk a road, so no board finishes within
+48 steps (measured: 0 of 40 at both sizes); those two shapes run 160 steps -- their first 48 are
+the 48-step run -- so that the auto-reset's observation is compared there too.
 """
 import copy
 import functools
@@ -129,7 +133,9 @@ def test_f16_obs_is_rounded_f32_obs(L, mode, multi, steps, kernel):
 
 
 # generic L: the quad path (L^2 % 4 == 0, 8-B-aligned boards) and the per-element path
-@pytest.mark.parametrize("L,mode,steps", [(12, "2p", 96), (11, "def", 64), (9, "atk", 64)])
+# and the ends of the size range: 32 (quad path, NC = 1024) and 31 (per-element path, NC = 961)
+@pytest.mark.parametrize("L,mode,steps", [(12, "2p", 96), (11, "def", 64), (9, "atk", 64), (32, "def", 160),
+                                          (31, "atk", 160)])
 def test_f16_obs_generic_map_size(L, mode, steps):
     _run(L, mode, False, steps, "auto")
 

@@ -132,7 +132,8 @@ def test_refill_kernel_layouts_match_host_sequence():
 
 
 
-@pytest.mark.parametrize("L,B,resets", [(10, 512, 10), (20, 128, 4)])
+# (32 and 8: the wave generator's scratch at the largest and the smallest side it can draw)
+@pytest.mark.parametrize("L,B,resets", [(10, 512, 10), (20, 128, 4), (32, 64, 3), (8, 128, 4)])
 def test_reset_sequence_matches_host(L, B, resets):
     """Explicit resets one after another (each draws the board's next layout, failing
     draws leaving the board as it was): the reset kernel's draws -- including the
