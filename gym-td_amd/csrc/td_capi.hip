@@ -21,6 +21,7 @@
 
 #include "../../include/tdstep.h"
 #include "../../include/td_diag.h"
+#include "td_copy_check.h"
 #include "td_kernels.h"
 #include "td_layout.h"
 #include "td_rng.h"
@@ -76,6 +77,7 @@ constexpr int kWalksPerStep = 3;
 constexpr int kGuardEvery = NSLOT - 1;
 constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw does not stall the next (the HIP
                                  // runtime has 4 hardware queues per process; the step stream needs one)
+constexpr int kCopySlots = 4;    // td_copy_boards: index uploads in flight before a call waits for the oldest
 
 }  // namespace
 
@@ -133,6 +135,14 @@ struct td_handle {
   bool retained_valid = false;     // every board's is known to be there
   std::vector<uint8_t> obs_known;  // [B] board b's is (a reset into the buffer wrote it, or a step)
   int n_known = 0;
+  // td_copy_boards: the caller's index arrays travel through kCopySlots pinned slots of 2 B ids
+  // in turn (allocated by td_create), each to d_pairs on the call's stream; a slot is
+  // written again only once the event behind its last upload has passed
+  int32_t* copy_stage = nullptr;  // pinned host [kCopySlots][2 B]
+  int32_t* d_pairs = nullptr;     // [2 B]: the sources, then the destinations
+  hipEvent_t copy_ev[kCopySlots] = {};
+  int copy_next = 0;
+  std::vector<uint8_t> copy_role;  // [B] copy_check's scratch
 };
 
 namespace {
@@ -566,6 +576,11 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
   rc |= dalloc(&h->d_epstats, 2);
   rc |= dalloc(&h->d_lastep, B);
   rc |= dalloc(&h->d_guard_to, 1);
+  rc |= dalloc(&h->d_pairs, 2 * B);
+  if (!rc && hipHostMalloc((void**)&h->copy_stage, kCopySlots * 2 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+    rc = fail("td_create: %zu B of pinned host memory (td_copy_boards' index slots)", kCopySlots * 2 * B * sizeof(int32_t));
+  for (int q = 0; q < kCopySlots && !rc; ++q)
+    if (hipEventCreateWithFlags(&h->copy_ev[q], hipEventDisableTiming) != hipSuccess) rc = fail("event");
   if (rc) {  // name the footprint (the staged-layout rings are most of it at large L)
     const double ring = (double)B * NSLOT * slot_words(map_size) * 4.0;
     const double total = (double)B * (sizeof(TdHdr) + ECAP * 20 + TCAP * 12 + (size_t)h->NC * 4 + 2 * OPP_WORDS * 4 +
@@ -631,6 +646,10 @@ void td_destroy(td_handle* h) {
                    h->d_guard_to};
   for (void* p : dptrs)
     if (p) (void)hipFree(p);
+  if (h->d_pairs) (void)hipFree(h->d_pairs);
+  if (h->copy_stage) (void)hipHostFree(h->copy_stage);
+  for (hipEvent_t e : h->copy_ev)
+    if (e) (void)hipEventDestroy(e);
   if (h->ev_main) (void)hipEventDestroy(h->ev_main);
   if (h->ev_step) (void)hipEventDestroy(h->ev_step);
   for (hipEvent_t e : h->tev) (void)hipEventDestroy(e);
@@ -854,6 +873,44 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
     HIP_OK(hipStreamSynchronize(s));
     for (int i = 0; mine && i < m; ++i) obs_mark(h, boards[i0 + i]);
   }
+  guard.ok = true;
+  return 0;
+}
+
+// Boards dst[i] become copies of boards src[i] on the device (td_copy.hip), asynchronously on
+// the step's stream.  The ids are checked here, before anything is enqueued; they reach the
+// kernel through a pinned slot and d_pairs, so the caller's arrays are free on return.
+int td_copy_boards(td_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, void* stream) {
+  if (!h) return fail("td_copy_boards: NULL handle");
+  char msg[200];
+  if (copy_check(src, dst, n, h->B, h->copy_role, msg, sizeof msg) != COPY_OK) return fail("td_copy_boards: %s", msg);
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  // the destinations' states change: rows written into the retained buffer keep it current,
+  // any other buffer (or none) leaves it behind
+  const bool mine = obs_reset_into(h, obs);
+  ObsGuard guard{h};
+  const size_t slot_ids = 2 * (size_t)h->B;
+  const int q = h->copy_next;
+  // (an event never recorded is complete; else this waits for the upload kCopySlots calls ago only)
+  HIP_OK(hipEventSynchronize(h->copy_ev[q]));
+  int32_t* stage = h->copy_stage + (size_t)q * slot_ids;
+  std::memcpy(stage, src, (size_t)n * sizeof(int32_t));
+  std::memcpy(stage + n, dst, (size_t)n * sizeof(int32_t));
+  HIP_OK(hipMemcpyAsync(h->d_pairs, stage, 2 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipEventRecord(h->copy_ev[q], s));
+  h->copy_next = (q + 1) % kCopySlots;
+  StepArgs a = base_args(h);
+  a.obs = obs;
+  // td_kernel_timing: a copy kernel's dispatch takes the next event pair too, whatever `every` is
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (h->tev_n < h->tev_cap) {
+    e0 = h->tev[2 * (size_t)h->tev_n];
+    e1 = h->tev[2 * (size_t)h->tev_n + 1];
+    h->tev_n += 1;
+  }
+  HIP_OK(launch_copy(a, h->d_pairs, n, s, e0, e1));
+  for (int i = 0; mine && i < n; ++i) obs_mark(h, dst[i]);  // (a destination without an episode is written whole by its next step)
   guard.ok = true;
   return 0;
 }

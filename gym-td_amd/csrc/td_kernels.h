@@ -1,5 +1,5 @@
 // td_kernels.h -- launch interface between the C-ABI (td_capi.hip) and the kernel units
-// (td_step.hip, td_step_f16.hip, td_reset.hip, td_mask.hip).
+// (td_step.hip, td_step_f16.hip, td_reset.hip, td_mask.hip, td_copy.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,7 +31,7 @@ struct StepArgs {
   uint32_t* cells;
   uint32_t* opp_mt;     // [B][626] CPython-random MT words of the built-in opponent ([624..625] unused)
   uint32_t* opp_hot;    // [B][HOT_WORDS] its position, lazy-twist boundary, count and next 8 draws
-  uint32_t* np_mt;      // [B][625] numpy-legacy state of the layout stream (TDGymBasic.np_random)
+  uint32_t* np_mt;      // [B][626] numpy-legacy state of the layout stream (TDGymBasic.np_random)
   // Staged next-episode layouts: a ring of NSLOT records per board (slot_words
   // words each, 128-B aligned).  Layout number n of a board's stream lives in slot
   // n % NSLOT with word 0 = slot_tag(n) once it is complete; lay_tail counts the
@@ -131,6 +131,12 @@ hipError_t launch_refill(const StepArgs& a, hipStream_t s, int guard = 0);
 // The built-in opponent (side 0: random_enemy_lv<level>, 1: random_tower_lv<level>)
 // on the boards in a.reset_mask (nullptr = all).
 hipError_t launch_opponent(const StepArgs& a, int side, int level, hipStream_t s);
+// Board copy (td_copy_boards; td_copy.hip): boards pairs[n + i] become copies of boards pairs[i],
+// i in [0, n), n >= 1; `pairs` is device memory, the ids validated by the caller.  With a.obs the
+// destinations' observation rows are written whole in the format a.obs_f16.
+// ev0 / ev1: optional timing events bound to the kernel's dispatch, as launch_step's.
+hipError_t launch_copy(const StepArgs& a, const int32_t* pairs, int n, hipStream_t s, hipEvent_t ev0 = nullptr,
+                       hipEvent_t ev1 = nullptr);
 
 // Legal-action masks of the boards' present state (td_action_mask; td_mask.hip): which
 // action the next step would execute.  Reads the header, the cell words (map[6] in bits

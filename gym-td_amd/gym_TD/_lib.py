@@ -94,6 +94,7 @@ def _load():
         "td_reset": (ctypes.c_int, [c_vp, c_u8p, c_vp, c_vp]),
         "td_last_reset_failures": (ctypes.c_int, [c_vp, c_i32p, ctypes.c_int]),
         "td_reset_layouts": (ctypes.c_int, [c_vp, c_u32p, c_i32p, ctypes.c_int, c_vp, c_vp]),
+        "td_copy_boards": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
         "td_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp]),
         "td_mask_io_init": (None, [ctypes.POINTER(TdMaskIO)]),
         "td_action_mask": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp]),

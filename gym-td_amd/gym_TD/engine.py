@@ -412,6 +412,34 @@ class TDEngine(object):
         self._keep = keep  # actions stay alive until the next call
         return self.obs, self.reward, self.done
 
+    def copy_boards(self, src, dst, write_obs=True):
+        """Make boards ``dst[i]`` exact copies of boards ``src[i]`` on the device
+        (td_copy_boards): the fork of a search -- one root repeated in ``src`` gives many
+        children.  The reference's counterpart is ``copy.deepcopy(env)``.
+
+        ``src`` / ``dst``: equally many board ids as int sequences, numpy arrays or tensors; a
+        GPU tensor is brought to the host first (a device-to-host copy that waits for that
+        tensor), so pass host ids where the call must not wait; int32 numpy arrays are taken as
+        they are, anything else is converted (O(n) on the host, as the library's check of the
+        ids is).  No board may be named twice
+        in ``dst`` or in both (TDError, nothing changes).  Header, live enemies and towers with
+        their config epochs, cells and the opponent's stream are copied; with
+        random_agent=True each destination keeps its own layout sequence for its next
+        episodes, with random_agent=False the shared numpy stream is copied too.
+
+        One kernel on torch's current stream, which must be the stream of step(); nothing is
+        synchronised.  With ``write_obs`` the destinations' observations are written whole
+        into ``self.obs`` (the rows of the sources' present states); without it nothing is
+        written and the next step writes every byte.  The engine's other last-step tensors
+        (``reward``, ``done``, the info tensors) keep ``dst``'s old rows until the next step.
+        Returns ``self.obs``."""
+        s, d = _board_ids(src), _board_ids(dst)
+        if s.shape != d.shape:
+            raise ValueError("src and dst must name equally many boards, got %d and %d" % (s.size, d.size))
+        _lib.check(_lib.lib.td_copy_boards(self._h, s.ctypes.data, d.ctypes.data, int(s.size),
+                                           self.obs.data_ptr() if write_obs else None, self._stream()))
+        return self.obs
+
     def action_mask(self, code=False):
         """Legal-action masks of every board's present state (td_action_mask): what the next
         step() would execute if the action were the only thing asked of that side.
@@ -622,6 +650,20 @@ def _check_frame_skip(k):
     if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= _lib.MAX_FRAME_SKIP:
         raise ValueError("frame_skip must be an int in [1, %d], not %r" % (_lib.MAX_FRAME_SKIP, k))
     return int(k)
+
+
+def _board_ids(x):
+    """Board ids (ints, numpy array, CPU or GPU tensor) -> contiguous int32 host array."""
+    if isinstance(x, torch.Tensor):
+        x = x.detach().cpu().numpy()
+    a = np.asarray(x).reshape(-1)
+    if a.dtype == np.int32:  # (the cheap way in: nothing is converted)
+        return np.ascontiguousarray(a)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("board ids must be integers, not %s" % a.dtype)
+    if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
+        raise ValueError("board id out of range")
+    return np.ascontiguousarray(a, dtype=np.int32)
 
 
 def _as_dev(x, dtype, device):

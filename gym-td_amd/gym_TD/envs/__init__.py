@@ -364,6 +364,17 @@ class TDVecEnv(object):
         self._masks = self.engine.action_mask()
         return self._masks
 
+    def fork(self, src, dst):
+        """Make envs ``dst[i]`` exact copies of envs ``src[i]`` between two steps, on the device
+        (TDEngine.copy_boards): search forks -- what ``copy.deepcopy(env)`` is to a reference
+        env.  Returns the observation tensor, the copies' rows written; with
+        ``action_mask=True`` the masks are computed again for the new states.  The last
+        step's reward, done and infos keep ``dst``'s old rows until the next step."""
+        obs = self.engine.copy_boards(src, dst)
+        if self.with_action_mask:
+            self._masks = self.engine.action_mask()
+        return obs
+
     def step(self, actions):
         if self.mode == "def":
             obs, rew, done = self.engine.step(def_act=actions)

@@ -302,6 +302,46 @@ int td_last_reset_failures(td_handle* h, int32_t* boards, int cap);
  * are taken as they are. */
 int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, int n, float* obs, void* stream);
 
+/* Copy board states on the device: after the call's work has run on `stream`, board dst[i] of
+ * this handle is board src[i], for every i in [0, n) -- the fork a search needs (expanding a
+ * node, rollouts from a common root, restarting a population from its best board).  The
+ * reference has no counterpart short of copy.deepcopy(env); the host form of the same is
+ * td_export_state + td_import_state, which waits for the device, retags the entities to the
+ * current config epoch, drops the pre-drawn opponent outputs and voids the retained observation.
+ * src / dst: host arrays of n board ids; they are the caller's again when the call returns.
+ * Copied, per pair: the whole 96-B header (flags, episodes, ep_return, cool-downs and the
+ *   captured max_cost / max_base_LP: the clone carries its source's history); the live enemy
+ *   slots [0, n_en) and tower slots [0, n_tw) (counts from the source's header, clamped to 128 /
+ *   32; slots at or past the count are unspecified, as after any step), config-epoch tags as
+ *   they are -- both boards read this handle's config blocks, and td_set_config counts the
+ *   clone's entities when it recycles a block; the L^2 cell words; the opponent's 626 stream
+ *   words and its hot record, pre-drawn outputs included.
+ * Not copied: with random_agent = 1 the destination keeps its own layout stream, staged
+ *   layouts and pending draw -- a fork is its source until the episode ends, then starts the
+ *   next episode of its OWN layout sequence.  With random_agent = 0 the numpy stream is the
+ *   opponent's too and nothing is staged ahead, so it is copied as well: the fork stays its
+ *   source through auto-resets.  The last-finished-episode records (td_episode_records) and the
+ *   episode statistics are never touched, nor is any td_step_io output of an earlier step.
+ * obs (device, may be NULL): the whole observation of every destination is written into row
+ *   dst[i], in the handle's format and with td_step's element and alignment rules -- what a full
+ *   write of that state under the current config leaves: bytewise the source's row after the
+ *   step that produced the state, unless td_set_config came between (which voids a retained
+ *   observation anyway).  The row of a destination whose source holds no episode (never successfully reset)
+ *   is left unwritten, as td_reset leaves the row of a board whose draw failed.  With
+ *   obs == td_retained_obs(h) the buffer stays retained and the rows written count as known;
+ *   any other obs, NULL included, leaves the retained buffer behind (the next step into it
+ *   writes every byte), as does a call that fails after its checks.
+ * Asynchronous on `stream`, which must be the step's stream (as for td_action_mask); the
+ *   device is not waited for.  (The ids are staged through four pinned slots of the handle in
+ *   turn; only a call issued while the upload four calls back is still pending waits, for that
+ *   upload.)  n == 0 returns 0 and launches nothing.
+ * Refused (< 0, td_last_error; checked on the host before anything is enqueued, so no board,
+ *   flag, observation byte or retention state changes): a NULL handle; NULL arrays with n > 0;
+ *   n < 0 or n > the handle's boards; an id outside [0, boards); a board named twice in dst; a
+ *   board named in both src and dst (the result would depend on pair order).  A board repeated
+ *   in src is the point of the call: one root, many children. */
+int td_copy_boards(td_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, void* stream);
+
 /* One env step for all boards (asynchronous on `stream`).  Buffers need only their
  * element type's alignment; a 16-B-aligned obs (and, multi-action, 16-B-aligned flag
  * and real-action arrays) takes the line-aligned 16-B store path, any other the
@@ -386,7 +426,8 @@ int td_set_refill_interval(td_handle* h, int steps);
  * binds a pair of timing events to its step kernel's own dispatch (hipExtLaunchKernel;
  * no marker packets); max_launches = 0 turns it off.  td_kernel_times waits for them
  * and writes each kernel's start-to-end duration in microseconds (the dispatch-packet
- * timestamps rocprofv3 reports); returns the count. */
+ * timestamps rocprofv3 reports); returns the count.  A td_copy_boards call made while pairs
+ * are left takes the next pair for its copy kernel as well, whatever `every` is. */
 int td_kernel_timing(td_handle* h, int max_launches, int every);
 int td_kernel_times(td_handle* h, float* us, int cap);
 
