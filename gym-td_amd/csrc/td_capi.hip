@@ -22,6 +22,7 @@
 #include "../../include/tdstep.h"
 #include "../../include/td_diag.h"
 #include "td_copy_check.h"
+#include "td_ids_check.h"
 #include "td_kernels.h"
 #include "td_layout.h"
 #include "td_rng.h"
@@ -90,6 +91,7 @@ struct td_handle {
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
   std::string kernel_name;    // td_step_kernel_name
+  std::string sel_kernel_name;  // td_step_boards_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -135,14 +137,14 @@ struct td_handle {
   bool retained_valid = false;     // every board's is known to be there
   std::vector<uint8_t> obs_known;  // [B] board b's is (a reset into the buffer wrote it, or a step)
   int n_known = 0;
-  // td_copy_boards: the caller's index arrays travel through kCopySlots pinned slots of 2 B ids
+  // td_copy_boards, td_step_boards: the caller's index arrays travel through kCopySlots pinned slots of 2 B ids
   // in turn (allocated by td_create), each to d_pairs on the call's stream; a slot is
   // written again only once the event behind its last upload has passed
   int32_t* copy_stage = nullptr;  // pinned host [kCopySlots][2 B]
   int32_t* d_pairs = nullptr;     // [2 B]: the sources, then the destinations
   hipEvent_t copy_ev[kCopySlots] = {};
   int copy_next = 0;
-  std::vector<uint8_t> copy_role;  // [B] copy_check's scratch
+  std::vector<uint8_t> copy_role;  // [B] copy_check's scratch, and ids_check's (td_step_boards): all zero between calls
 };
 
 namespace {
@@ -915,20 +917,27 @@ int td_copy_boards(td_handle* h, const int32_t* src, const int32_t* dst, int n, 
   return 0;
 }
 
-int td_step(td_handle* h, const td_step_io* io, void* stream) {
-  if (!io) return fail("td_step: NULL io");
+namespace {
+
+// What td_step and td_step_boards check of their io before anything else, and the step
+// arguments they make of it.  fn: the caller's name, for the message.
+int check_step_io(const char* fn, const td_handle* h, const td_step_io* io) {
+  if (!io) return fail("%s: NULL io", fn);
   // The two header words first (every td_step_io of any ABI has >= 8 bytes): a caller
   // built against another layout is refused before any pointer of its struct is read.
   if (io->size != (uint32_t)sizeof(td_step_io) || io->abi != (uint32_t)TD_ABI_VERSION)
-    return fail("td_step: td_step_io has size %u / abi %u, this library expects size %u / abi %d "
+    return fail("%s: td_step_io has size %u / abi %u, this library expects size %u / abi %d "
                 "(set io.size = sizeof(td_step_io) and io.abi = TD_ABI_VERSION, or call td_step_io_init; "
                 "an ABI-2 struct has no header)",
-                io->size, io->abi, (unsigned)sizeof(td_step_io), TD_ABI_VERSION);
-  if (!h) return fail("td_step: NULL handle");
-  if (!io->obs || !io->reward || !io->done) return fail("td_step: obs, reward and done are required");
-  if (h->mode != TD_MODE_ATK && !io->def_act) return fail("td_step: def_act required in this mode");
-  if (h->mode != TD_MODE_DEF && !io->atk_act) return fail("td_step: atk_act required in this mode");
-  hipStream_t s = (hipStream_t)stream;
+                fn, io->size, io->abi, (unsigned)sizeof(td_step_io), TD_ABI_VERSION);
+  if (!h) return fail("%s: NULL handle", fn);
+  if (!io->obs || !io->reward || !io->done) return fail("%s: obs, reward and done are required", fn);
+  if (h->mode != TD_MODE_ATK && !io->def_act) return fail("%s: def_act required in this mode", fn);
+  if (h->mode != TD_MODE_DEF && !io->atk_act) return fail("%s: atk_act required in this mode", fn);
+  return 0;
+}
+
+StepArgs step_args(td_handle* h, const td_step_io* io) {
   StepArgs a = base_args(h);
   a.def_act = io->def_act; a.atk_act = io->atk_act; a.obs = io->obs; a.reward = io->reward; a.done = io->done;
   a.real_def = io->real_def; a.real_atk = io->real_atk; a.fail_def = io->fail_def; a.fail_atk = io->fail_atk;
@@ -936,23 +945,40 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   a.cooldowns = io->cooldowns;
   a.ep_stats = h->d_epstats;
   a.last_ep = h->d_lastep;
+  return a;
+}
+
+// What goes in front of a step launch on its stream: the side refill at its cadence and the
+// ring guard (kGuardEvery).  Both count launches: a board consumes at most one staged layout
+// per launch, whether the launch steps every board or some.
+int before_step_launch(td_handle* h, const StepArgs& a, hipStream_t s) {
+  // the refill goes first: it waits for the previous step only, so a board whose ring
+  // is dry in this step can wait for it (td_step_body.h step_board) without a cycle
+  // random_agent=True: layouts are staged ahead by refills on the side streams.
+  // random_agent=False: they are drawn in stream order right after the step (td_step).
+  if (h->autoreset && !h->opp_np && h->refill_every > 0 && (h->steps % h->refill_every) == 0 &&
+      start_refill(h, s, true))
+    return -1;
+  // the ring guard: behind the previous step, beside the refill just launched
+  if (h->autoreset && !h->opp_np && h->guard_every > 0 && h->since_guard >= h->guard_every) {
+    HIP_OK(launch_refill(a, s, h->guard_every));
+    h->since_guard = 0;
+  }
+  return 0;
+}
+
+}  // namespace
+
+int td_step(td_handle* h, const td_step_io* io, void* stream) {
+  if (check_step_io("td_step", h, io)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  StepArgs a = step_args(h, io);
   // td_retain_obs: a step into the retained buffer may skip what the buffer already holds;
   // any other step writes every byte and leaves the retained buffer behind.
   const bool retained = h->retained && (const void*)io->obs == h->retained;
   a.obs_skip = retained && h->retained_valid ? 1 : 0;
   ObsGuard guard{h};
-  // the refill goes first: it waits for the previous step only, so a board whose ring
-  // is dry in this step can wait for it (td_step_body.h step_board) without a cycle
-  // random_agent=True: layouts are staged ahead by refills on the side streams.
-  // random_agent=False: they are drawn in stream order right after the step (below).
-  if (h->autoreset && !h->opp_np && h->refill_every > 0 && (h->steps % h->refill_every) == 0 &&
-      start_refill(h, s, true))
-    return -1;
-  // the ring guard (kGuardEvery): behind the previous step, beside the refill just launched
-  if (h->autoreset && !h->opp_np && h->guard_every > 0 && h->since_guard >= h->guard_every) {
-    HIP_OK(launch_refill(a, s, h->guard_every));
-    h->since_guard = 0;
-  }
+  if (before_step_launch(h, a, s)) return -1;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->tev_n < h->tev_cap && (h->steps - h->tev_from) % h->tev_every == 0) {
     e0 = h->tev[2 * (size_t)h->tev_n];
@@ -969,6 +995,62 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   else if (!h->retained_valid) obs_mark_all(h);  // every board's observation is in the retained buffer now
   guard.ok = true;
   return 0;
+}
+
+// One env step for the boards named, every other board left as it is (td_step_sel.hip),
+// asynchronously on the step's stream.  Everything is checked here, before anything is enqueued;
+// the ids reach the kernel through td_copy_boards' pinned slots and d_pairs, so the caller's
+// array is free on return.
+int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, int n, void* stream) {
+  if (check_step_io("td_step_boards", h, io)) return -1;
+  if (h->frame_skip > 1)
+    return fail("td_step_boards: not supported with frame skip (td_frame_skip() = %d); set td_set_frame_skip(h, 1) first",
+                h->frame_skip);
+  if (h->opp_np && h->autoreset)
+    return fail("td_step_boards: not supported with random_agent = 0 and auto-reset on (the reset kernel behind a step "
+                "goes by done[] of every board, and an unnamed board's is stale)");
+  char msg[200];
+  if (ids_check(boards, n, h->B, h->copy_role, msg, sizeof msg) != IDS_OK) return fail("td_step_boards: %s", msg);
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  StepArgs a = step_args(h, io);
+  // td_retain_obs: a step into the retained buffer may skip what the buffer already holds of
+  // the boards it steps; into any other buffer it leaves the retained buffer behind.
+  const bool retained = h->retained && (const void*)io->obs == h->retained;
+  bool known = retained && (h->retained_valid || h->obs_known.size() == (size_t)h->B);
+  for (int i = 0; known && !h->retained_valid && i < n; ++i) known = h->obs_known[(size_t)boards[i]] != 0;
+  a.obs_skip = known ? 1 : 0;
+  ObsGuard guard{h};
+  const int q = h->copy_next;
+  // (an event never recorded is complete; else this waits for the upload kCopySlots calls ago only)
+  HIP_OK(hipEventSynchronize(h->copy_ev[q]));
+  int32_t* stage = h->copy_stage + (size_t)q * 2 * (size_t)h->B;
+  std::memcpy(stage, boards, (size_t)n * sizeof(int32_t));
+  if (before_step_launch(h, a, s)) return -1;
+  HIP_OK(hipMemcpyAsync(h->d_pairs, stage, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipEventRecord(h->copy_ev[q], s));
+  h->copy_next = (q + 1) % kCopySlots;
+  // td_kernel_timing: the kernel's dispatch takes the next event pair, whatever `every` is (as the copy's)
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (h->tev_n < h->tev_cap) {
+    e0 = h->tev[2 * (size_t)h->tev_n];
+    e1 = h->tev[2 * (size_t)h->tev_n + 1];
+    h->tev_n += 1;
+  }
+  HIP_OK(launch_step_sel(a, h->d_pairs, n, s, e0, e1));
+  h->steps += 1;
+  h->since_guard += 1;
+  if (!retained) obs_touch(h);
+  else
+    for (int i = 0; !known && i < n; ++i) obs_mark(h, boards[i]);  // written whole just now
+  guard.ok = true;
+  return 0;
+}
+
+const char* td_step_boards_kernel_name(td_handle* h) {
+  if (!h) return "";
+  h->sel_kernel_name = step_sel_kernel_name(base_args(h));
+  return h->sel_kernel_name.c_str();
 }
 
 void td_mask_io_init(td_mask_io* io) {

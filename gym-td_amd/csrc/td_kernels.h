@@ -1,5 +1,6 @@
 // td_kernels.h -- launch interface between the C-ABI (td_capi.hip) and the kernel units
-// (td_step.hip, td_step_f16.hip, td_reset.hip, td_mask.hip, td_copy.hip).
+// (td_step.hip, td_step_f16.hip, td_step_sel.hip, td_step_sel_f16.hip, td_reset.hip, td_mask.hip,
+// td_copy.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -117,6 +118,15 @@ hipError_t launch_skip(const StepArgs& a, hipStream_t s, hipEvent_t ev0 = nullpt
 std::string skip_kernel_name(const StepArgs& a);
 hipError_t launch_skip_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
 std::string skip_kernel_name_f16(const StepArgs& a);
+// Partial step (td_step_boards; td_step_sel.hip, td_step_sel_f16.hip): one env step for boards
+// ids[0 .. n), n >= 1, every other board left as it is; `ids` is device memory, the ids
+// validated by the caller.  One wave per list entry, the large kernel's shape, in the format
+// a.obs_f16; and that kernel's name as a profiler prints it.  frame_skip = 1 only.
+hipError_t launch_step_sel(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0 = nullptr,
+                           hipEvent_t ev1 = nullptr);
+std::string step_sel_kernel_name(const StepArgs& a);
+hipError_t launch_step_sel_f16(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
+std::string step_sel_kernel_name_f16(const StepArgs& a);
 // TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
 hipError_t launch_reset(const StepArgs& a, hipStream_t s);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),

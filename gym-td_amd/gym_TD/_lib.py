@@ -96,6 +96,7 @@ def _load():
         "td_reset_layouts": (ctypes.c_int, [c_vp, c_u32p, c_i32p, ctypes.c_int, c_vp, c_vp]),
         "td_copy_boards": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
         "td_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp]),
+        "td_step_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp, ctypes.c_int, c_vp]),
         "td_mask_io_init": (None, [ctypes.POINTER(TdMaskIO)]),
         "td_action_mask": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
@@ -118,6 +119,7 @@ def _load():
         "td_frame_skip": (ctypes.c_int, [c_vp]),
         "td_step_kernel": (ctypes.c_int, [c_vp]),
         "td_step_kernel_name": (ctypes.c_char_p, [c_vp]),
+        "td_step_boards_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_config_epoch": (ctypes.c_int, [c_vp]),
         "td_kernel_timing": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
         "td_kernel_times": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),

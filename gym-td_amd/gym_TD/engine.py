@@ -381,6 +381,29 @@ class TDEngine(object):
         (clone them to keep a history).  The returned obs tensor is the engine's buffer:
         read it, do not write it -- with retain_obs (the default) the next step leaves
         unwritten whatever it knows its last write left there."""
+        return self._launch_step(def_act, atk_act)
+
+    def step_boards(self, boards, def_act=None, atk_act=None):
+        """One step of the boards named in ``boards`` only (td_step_boards): exactly the step
+        ``step()`` would have given each of them, while every other board keeps its state, its
+        streams and its rows of every output tensor -- with ``copy_boards`` the loop of a
+        search: fork the leaves, step the leaves, read their rows.  The reference's
+        counterpart is ``child.step(a)`` on the env objects one chooses.
+
+        ``boards``: board ids as an int sequence, numpy array or tensor (``copy_boards``' rules:
+        a GPU tensor is brought to the host first; int32 numpy arrays are taken as they are),
+        in any order, none twice.  The actions are full-batch tensors of the shapes ``step()``
+        checks; only the rows of the named boards are read.  Returns (obs, reward, done), the
+        engine's own full tensors with only the named rows fresh; the info tensors likewise.
+
+        One kernel on torch's current stream, which must be the stream of step(); nothing is
+        synchronised (with ``host_io`` the call waits for the kernel, as ``step()`` does).  An
+        empty list is a no-op.  TDError, with nothing changed: an id out of range or named
+        twice, ``frame_skip`` > 1, random_agent=False with auto-reset on."""
+        return self._launch_step(def_act, atk_act, _board_ids(boards))
+
+    def _launch_step(self, def_act, atk_act, ids=None):
+        """step() (ids None) or step_boards(): stage the actions, launch, hand out the tensors."""
         io = self._io
         keep = []
         if self.host_io:
@@ -390,7 +413,8 @@ class TDEngine(object):
             if self.mode != "def":
                 self._atk_np[...] = np.asarray(atk_act, dtype=np.int64).reshape(self._atk_np.shape)
                 io.atk_act = self._atk_in.data_ptr()
-            _lib.check(_lib.lib.td_step(self._h, io, self._stream()))
+            _lib.check(_lib.lib.td_step(self._h, io, self._stream()) if ids is None else
+                       _lib.lib.td_step_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
             # the outputs are the caller's as soon as this returns, and the next call
             # rewrites the staged actions: wait for the kernel
             torch.cuda.current_stream(self.device).synchronize()
@@ -408,7 +432,8 @@ class TDEngine(object):
                 raise ValueError("attacker action must have shape (B, 3, 8)")
             keep.append(a)
             io.atk_act = a.data_ptr()
-        _lib.check(_lib.lib.td_step(self._h, io, self._stream()))
+        _lib.check(_lib.lib.td_step(self._h, io, self._stream()) if ids is None else
+                   _lib.lib.td_step_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
         self._keep = keep  # actions stay alive until the next call
         return self.obs, self.reward, self.done
 

@@ -376,16 +376,27 @@ class TDVecEnv(object):
         return obs
 
     def step(self, actions):
+        return self._step(actions, self.engine.step)
+
+    def step_boards(self, boards, actions):
+        """step() for the envs named in ``boards`` only (TDEngine.step_boards): ``actions`` as
+        for step(), full-batch, read at the named rows; every other env keeps its state and
+        its rows.  Returns step()'s tuple, the full tensors with the named rows fresh; with
+        ``action_mask=True`` the masks are computed again.  With fork() the loop of a search:
+        fork the leaves, step the leaves, read their rows and masks."""
+        return self._step(actions, lambda **kw: self.engine.step_boards(boards, **kw))
+
+    def _step(self, actions, run):
         if self.mode == "def":
-            obs, rew, done = self.engine.step(def_act=actions)
+            obs, rew, done = run(def_act=actions)
         elif self.mode == "atk":
-            obs, rew, done = self.engine.step(atk_act=actions)
+            obs, rew, done = run(atk_act=actions)
         else:
             if isinstance(actions, dict):
                 d, a = actions["Defender"], actions["Attacker"]
             else:
                 d, a = actions
-            obs, rew, done = self.engine.step(def_act=d, atk_act=a)
+            obs, rew, done = run(def_act=d, atk_act=a)
         e = self.engine
         infos = {}
         if e.info_enabled:

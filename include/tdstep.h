@@ -348,6 +348,41 @@ int td_copy_boards(td_handle* h, const int32_t* src, const int32_t* dst, int n, 
  * per-element one (same bytes, slower). */
 int td_step(td_handle* h, const td_step_io* io, void* stream);
 
+/* One env step for the boards boards[0 .. n) only -- exactly the step td_step would have given
+ * each of them -- while every other board keeps every byte of its state, both RNG streams, its
+ * staged layouts and its flags: the other half of a search iteration beside td_copy_boards (fork
+ * the leaves, step the leaves, read their rows and masks), as a reference user steps exactly the
+ * env objects they choose (copy.deepcopy(env), then child.step(a)).
+ * io: td_step's struct, with the same required pointers and the same size / abi check made
+ *   first.  Every array keeps its full-batch shape and is indexed by board id: actions are read
+ *   from the rows of the named boards only, and outputs (obs, reward, done, real / fail, win,
+ *   allow_next, cooldowns, ep_return, ep_len) are written to those rows only -- no byte of an
+ *   unnamed row changes, the observation lines it shares with a named neighbour included.
+ *   td_episode_stats / td_episode_records count and record the named boards only.
+ * boards: a host array of n board ids, the caller's again when the call returns (staged through
+ *   td_copy_boards' four pinned slots and uploaded on `stream` in front of the kernel).  Order
+ *   is free and the results do not depend on it.  n == 0 returns 0, launches nothing and counts
+ *   as no launch.
+ * The kernel: one wave per named board in td_step's TD_KERNEL_LARGE shape, whatever kind
+ *   td_step launches (td_step_boards_kernel_name); an obs buffer unaligned for its
+ *   format takes the per-element path, as in td_step.  A named board that was never reset
+ *   behaves as in td_step: zero row, done = 1, TD_FLAG_NO_LAYOUT.
+ * The call counts as a launch for the refill cadence and the ring guard (a board consumes at
+ *   most one staged layout per launch, whether the launch steps every board or some), and with
+ *   td_kernel_timing pairs left its kernel takes the next pair, whatever `every` is.
+ * Retained observation: with io->obs == td_retained_obs(h) the kernel skips clean windows only
+ *   if every named board's row is known to hold its last observation; afterwards the named
+ *   boards' rows are known and the buffer stays retained.  A step into any other buffer leaves
+ *   the retained buffer behind (the next step into it writes every byte), as td_step does.
+ * Asynchronous on `stream`, which must be the step's stream.
+ * Refused (< 0, td_last_error; checked on the host before anything is enqueued, so no board,
+ *   flag, observation byte or retention state changes): a NULL handle or io, or a bad size / abi
+ *   word; missing required pointers; NULL boards with n > 0; n < 0 or n > the handle's boards;
+ *   an id outside [0, boards); an id named twice (two waves on one board would race);
+ *   td_frame_skip() > 1; random_agent = 0 with auto-reset on (the reset kernel behind a step
+ *   goes by done[] of every board, and an unnamed board's is stale). */
+int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, int n, void* stream);
+
 /* Legal-action masks: for every board and every action, whether the NEXT td_step would
  * execute that action if it were the only thing asked of that side -- decided on the device
  * from the board's present state with the step's own comparisons, so a policy can sample
@@ -413,6 +448,11 @@ int td_action_mask(td_handle* h, const td_mask_io* io, void* stream);
 enum td_step_kernel_kind { TD_KERNEL_AUTO = 0, TD_KERNEL_LARGE = 1, TD_KERNEL_SMALL = 2, TD_KERNEL_SMALL2 = 3 };
 int td_step_kernel(td_handle* h);
 const char* td_step_kernel_name(td_handle* h);
+/* The kernel td_step_boards launches on this handle, as rocprofv3 shows it:
+ * "td_step_sel_kernel<10, 0, false>" (L or 0 for a generic side, mode, multi-action scan), or
+ * "td_step_sel_kernel_f16<...>" with TD_OBS_F16: one wave per named board in TD_KERNEL_LARGE's
+ * shape, whatever kind td_step launches.  The string is the handle's, valid until the next call. */
+const char* td_step_boards_kernel_name(td_handle* h);
 
 /* Steps between launches of the layout refill kernel on the side streams (auto-reset;
  * default 64, 0 = none).  A pure performance knob: before every 15th step (and the first
