@@ -26,6 +26,7 @@
 #include "td_kernels.h"
 #include "td_layout.h"
 #include "td_rng.h"
+#include "td_step_launch.h"
 
 using namespace td;
 
@@ -78,7 +79,7 @@ constexpr int kWalksPerStep = 3;
 constexpr int kGuardEvery = NSLOT - 1;
 constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw does not stall the next (the HIP
                                  // runtime has 4 hardware queues per process; the step stream needs one)
-constexpr int kCopySlots = 4;    // td_copy_boards: index uploads in flight before a call waits for the oldest
+constexpr int kIdSlots = 4;      // td_copy_boards, td_step_boards: id uploads in flight before a call waits for the oldest
 
 }  // namespace
 
@@ -137,14 +138,14 @@ struct td_handle {
   bool retained_valid = false;     // every board's is known to be there
   std::vector<uint8_t> obs_known;  // [B] board b's is (a reset into the buffer wrote it, or a step)
   int n_known = 0;
-  // td_copy_boards, td_step_boards: the caller's index arrays travel through kCopySlots pinned slots of 2 B ids
+  // td_copy_boards, td_step_boards: the caller's id arrays travel through kIdSlots pinned slots of 2 B ids
   // in turn (allocated by td_create), each to d_pairs on the call's stream; a slot is
-  // written again only once the event behind its last upload has passed
-  int32_t* copy_stage = nullptr;  // pinned host [kCopySlots][2 B]
-  int32_t* d_pairs = nullptr;     // [2 B]: the sources, then the destinations
-  hipEvent_t copy_ev[kCopySlots] = {};
-  int copy_next = 0;
-  std::vector<uint8_t> copy_role;  // [B] copy_check's scratch, and ids_check's (td_step_boards): all zero between calls
+  // written again only once the event behind its last upload has passed (upload_ids)
+  int32_t* id_stage = nullptr;  // pinned host [kIdSlots][2 B]
+  int32_t* d_pairs = nullptr;   // [2 B]: a copy's sources, then its destinations; or a partial step's boards
+  hipEvent_t id_ev[kIdSlots] = {};
+  int id_next = 0;
+  std::vector<uint8_t> id_role;  // [B] copy_check's scratch, and ids_check's: all zero between calls
 };
 
 namespace {
@@ -322,7 +323,9 @@ int apply_kernel(td_handle* h, int small) {
   // slower steps at 16,384-65,536 boards, profiles/r03/s21.)
   h->obs_wt = h->small && obs_bytes <= 192.0 * 1024 * 1024 ? 1 : 0;
   // (while frame skip is on, td_step launches the skip kernel whatever kind is kept here)
-  h->kernel_name = h->frame_skip > 1 ? skip_kernel_name(base_args(h)) : step_kernel_name(base_args(h));
+  // (for an aligned observation buffer: launch_step takes the large kernel for any other)
+  const StepArgs a = base_args(h);
+  h->kernel_name = kernel_display_name(h->frame_skip > 1 ? skip_row(a) : step_row(a, a.small));
   return 0;
 }
 
@@ -409,10 +412,41 @@ int run_reset(td_handle* h, const std::vector<uint8_t>& mask, float* obs, hipStr
   StepArgs a = base_args(h);
   a.obs = obs;
   a.reset_mask = h->d_mask;
-  HIP_OK(launch_step(a, s, true));
+  HIP_OK(launch_reset(a, s));
   h->since_guard = kGuardEvery;  // a reset consumed layouts: guard before the next step
   if (h->autoreset && !h->opp_np && start_refill(h, s)) return -1;
   HIP_OK(hipDeviceSynchronize());
+  return 0;
+}
+
+// td_kernel_timing: the event pair of the next timed dispatch, or none once tev_cap are out.
+// td_copy_boards and td_step_boards take one whatever `every` is; td_step asks at its cadence.
+struct EvPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+};
+EvPair next_timing_pair(td_handle* h) {
+  EvPair p;
+  if (h->tev_n < h->tev_cap) {
+    p.e0 = h->tev[2 * (size_t)h->tev_n];
+    p.e1 = h->tev[2 * (size_t)h->tev_n + 1];
+    h->tev_n += 1;
+  }
+  return p;
+}
+
+// The caller's ids to d_pairs on the call's stream, through the next pinned slot, so the
+// caller's arrays are free on return: ids0[0 .. n), then ids1[0 .. n) where given.
+int upload_ids(td_handle* h, const int32_t* ids0, const int32_t* ids1, int n, hipStream_t s) {
+  const int q = h->id_next;
+  // (an event never recorded is complete; else this waits for the upload kIdSlots calls ago only)
+  HIP_OK(hipEventSynchronize(h->id_ev[q]));
+  int32_t* stage = h->id_stage + (size_t)q * 2 * (size_t)h->B;
+  const size_t bytes = (size_t)n * sizeof(int32_t);
+  std::memcpy(stage, ids0, bytes);
+  if (ids1) std::memcpy(stage + n, ids1, bytes);
+  HIP_OK(hipMemcpyAsync(h->d_pairs, stage, ids1 ? 2 * bytes : bytes, hipMemcpyHostToDevice, s));
+  HIP_OK(hipEventRecord(h->id_ev[q], s));
+  h->id_next = (q + 1) % kIdSlots;
   return 0;
 }
 
@@ -579,10 +613,10 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
   rc |= dalloc(&h->d_lastep, B);
   rc |= dalloc(&h->d_guard_to, 1);
   rc |= dalloc(&h->d_pairs, 2 * B);
-  if (!rc && hipHostMalloc((void**)&h->copy_stage, kCopySlots * 2 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-    rc = fail("td_create: %zu B of pinned host memory (td_copy_boards' index slots)", kCopySlots * 2 * B * sizeof(int32_t));
-  for (int q = 0; q < kCopySlots && !rc; ++q)
-    if (hipEventCreateWithFlags(&h->copy_ev[q], hipEventDisableTiming) != hipSuccess) rc = fail("event");
+  if (!rc && hipHostMalloc((void**)&h->id_stage, kIdSlots * 2 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+    rc = fail("td_create: %zu B of pinned host memory (td_copy_boards' index slots)", kIdSlots * 2 * B * sizeof(int32_t));
+  for (int q = 0; q < kIdSlots && !rc; ++q)
+    if (hipEventCreateWithFlags(&h->id_ev[q], hipEventDisableTiming) != hipSuccess) rc = fail("event");
   if (rc) {  // name the footprint (the staged-layout rings are most of it at large L)
     const double ring = (double)B * NSLOT * slot_words(map_size) * 4.0;
     const double total = (double)B * (sizeof(TdHdr) + ECAP * 20 + TCAP * 12 + (size_t)h->NC * 4 + 2 * OPP_WORDS * 4 +
@@ -649,8 +683,8 @@ void td_destroy(td_handle* h) {
   for (void* p : dptrs)
     if (p) (void)hipFree(p);
   if (h->d_pairs) (void)hipFree(h->d_pairs);
-  if (h->copy_stage) (void)hipHostFree(h->copy_stage);
-  for (hipEvent_t e : h->copy_ev)
+  if (h->id_stage) (void)hipHostFree(h->id_stage);
+  for (hipEvent_t e : h->id_ev)
     if (e) (void)hipEventDestroy(e);
   if (h->ev_main) (void)hipEventDestroy(h->ev_main);
   if (h->ev_step) (void)hipEventDestroy(h->ev_step);
@@ -870,7 +904,7 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
     a.reset_mask = h->d_mask;
     a.ovr_idx = h->d_ovr_idx;
     a.ovr_rec = h->d_stage;
-    HIP_OK(launch_step(a, s, true));
+    HIP_OK(launch_reset(a, s));
     h->since_guard = kGuardEvery;
     HIP_OK(hipStreamSynchronize(s));
     for (int i = 0; mine && i < m; ++i) obs_mark(h, boards[i0 + i]);
@@ -885,33 +919,18 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
 int td_copy_boards(td_handle* h, const int32_t* src, const int32_t* dst, int n, float* obs, void* stream) {
   if (!h) return fail("td_copy_boards: NULL handle");
   char msg[200];
-  if (copy_check(src, dst, n, h->B, h->copy_role, msg, sizeof msg) != COPY_OK) return fail("td_copy_boards: %s", msg);
+  if (copy_check(src, dst, n, h->B, h->id_role, msg, sizeof msg) != COPY_OK) return fail("td_copy_boards: %s", msg);
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   // the destinations' states change: rows written into the retained buffer keep it current,
   // any other buffer (or none) leaves it behind
   const bool mine = obs_reset_into(h, obs);
   ObsGuard guard{h};
-  const size_t slot_ids = 2 * (size_t)h->B;
-  const int q = h->copy_next;
-  // (an event never recorded is complete; else this waits for the upload kCopySlots calls ago only)
-  HIP_OK(hipEventSynchronize(h->copy_ev[q]));
-  int32_t* stage = h->copy_stage + (size_t)q * slot_ids;
-  std::memcpy(stage, src, (size_t)n * sizeof(int32_t));
-  std::memcpy(stage + n, dst, (size_t)n * sizeof(int32_t));
-  HIP_OK(hipMemcpyAsync(h->d_pairs, stage, 2 * (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipEventRecord(h->copy_ev[q], s));
-  h->copy_next = (q + 1) % kCopySlots;
+  if (upload_ids(h, src, dst, n, s)) return -1;
   StepArgs a = base_args(h);
   a.obs = obs;
-  // td_kernel_timing: a copy kernel's dispatch takes the next event pair too, whatever `every` is
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->tev_n < h->tev_cap) {
-    e0 = h->tev[2 * (size_t)h->tev_n];
-    e1 = h->tev[2 * (size_t)h->tev_n + 1];
-    h->tev_n += 1;
-  }
-  HIP_OK(launch_copy(a, h->d_pairs, n, s, e0, e1));
+  const EvPair ev = next_timing_pair(h);  // a copy kernel's dispatch is timed too, whatever `every` is
+  HIP_OK(launch_copy(a, h->d_pairs, n, s, ev.e0, ev.e1));
   for (int i = 0; mine && i < n; ++i) obs_mark(h, dst[i]);  // (a destination without an episode is written whole by its next step)
   guard.ok = true;
   return 0;
@@ -979,15 +998,10 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   a.obs_skip = retained && h->retained_valid ? 1 : 0;
   ObsGuard guard{h};
   if (before_step_launch(h, a, s)) return -1;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->tev_n < h->tev_cap && (h->steps - h->tev_from) % h->tev_every == 0) {
-    e0 = h->tev[2 * (size_t)h->tev_n];
-    e1 = h->tev[2 * (size_t)h->tev_n + 1];
-    h->tev_n += 1;
-  }
+  const EvPair ev = (h->steps - h->tev_from) % h->tev_every == 0 ? next_timing_pair(h) : EvPair{};
   // frame skip: one launch of the skip kernel runs the k board steps (td_step_skip.h).  The refill
   // cadence and the ring guard above count launches: a board consumes at most one layout per launch.
-  HIP_OK(h->frame_skip > 1 ? launch_skip(a, s, e0, e1) : launch_step(a, s, false, e0, e1));
+  HIP_OK(h->frame_skip > 1 ? launch_skip(a, s, ev.e0, ev.e1) : launch_step(a, s, ev.e0, ev.e1));
   if (h->autoreset && h->opp_np) HIP_OK(launch_autoreset(a, s));
   h->steps += 1;
   h->since_guard += 1;
@@ -999,7 +1013,7 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
 
 // One env step for the boards named, every other board left as it is (td_step_sel.hip),
 // asynchronously on the step's stream.  Everything is checked here, before anything is enqueued;
-// the ids reach the kernel through td_copy_boards' pinned slots and d_pairs, so the caller's
+// the ids reach the kernel through the pinned id slots and d_pairs (upload_ids), so the caller's
 // array is free on return.
 int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, int n, void* stream) {
   if (check_step_io("td_step_boards", h, io)) return -1;
@@ -1010,7 +1024,7 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
     return fail("td_step_boards: not supported with random_agent = 0 and auto-reset on (the reset kernel behind a step "
                 "goes by done[] of every board, and an unnamed board's is stale)");
   char msg[200];
-  if (ids_check(boards, n, h->B, h->copy_role, msg, sizeof msg) != IDS_OK) return fail("td_step_boards: %s", msg);
+  if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("td_step_boards: %s", msg);
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
   StepArgs a = step_args(h, io);
@@ -1021,23 +1035,10 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
   for (int i = 0; known && !h->retained_valid && i < n; ++i) known = h->obs_known[(size_t)boards[i]] != 0;
   a.obs_skip = known ? 1 : 0;
   ObsGuard guard{h};
-  const int q = h->copy_next;
-  // (an event never recorded is complete; else this waits for the upload kCopySlots calls ago only)
-  HIP_OK(hipEventSynchronize(h->copy_ev[q]));
-  int32_t* stage = h->copy_stage + (size_t)q * 2 * (size_t)h->B;
-  std::memcpy(stage, boards, (size_t)n * sizeof(int32_t));
-  if (before_step_launch(h, a, s)) return -1;
-  HIP_OK(hipMemcpyAsync(h->d_pairs, stage, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  HIP_OK(hipEventRecord(h->copy_ev[q], s));
-  h->copy_next = (q + 1) % kCopySlots;
-  // td_kernel_timing: the kernel's dispatch takes the next event pair, whatever `every` is (as the copy's)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (h->tev_n < h->tev_cap) {
-    e0 = h->tev[2 * (size_t)h->tev_n];
-    e1 = h->tev[2 * (size_t)h->tev_n + 1];
-    h->tev_n += 1;
-  }
-  HIP_OK(launch_step_sel(a, h->d_pairs, n, s, e0, e1));
+  // on the stream: the refill and the ring guard, then the ids, then the kernel
+  if (before_step_launch(h, a, s) || upload_ids(h, boards, nullptr, n, s)) return -1;
+  const EvPair ev = next_timing_pair(h);  // whatever `every` is (as the copy's)
+  HIP_OK(launch_step_sel(a, h->d_pairs, n, s, ev.e0, ev.e1));
   h->steps += 1;
   h->since_guard += 1;
   if (!retained) obs_touch(h);
@@ -1049,7 +1050,7 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
 
 const char* td_step_boards_kernel_name(td_handle* h) {
   if (!h) return "";
-  h->sel_kernel_name = step_sel_kernel_name(base_args(h));
+  h->sel_kernel_name = kernel_display_name(sel_row(base_args(h)));
   return h->sel_kernel_name.c_str();
 }
 

@@ -1,10 +1,8 @@
-// td_kernels.h -- launch interface between the C-ABI (td_capi.hip) and the kernel units
-// (td_step.hip, td_step_f16.hip, td_step_sel.hip, td_step_sel_f16.hip, td_reset.hip, td_mask.hip,
-// td_copy.hip).
+// td_kernels.h -- interface between the C-ABI (td_capi.hip) and the kernel units: the kernels'
+// arguments, the row lookups of the step, frame-skip and partial-step units (launched through
+// td_step_launch.h) and the launch_* functions of td_reset.hip, td_mask.hip and td_copy.hip.
 #pragma once
 #include <hip/hip_runtime.h>
-
-#include <string>
 
 #include "td_common.h"
 #include "../../include/tdstep.h"
@@ -96,37 +94,26 @@ __host__ __device__ inline int xcd_board(int i, int B) {
   return x * q + (x < r ? x : r) + i / NXCD;
 }
 
+// One row of the launch table of the step, frame-skip and partial-step kernels
+// (td_step_launch.h: selection, launch, occupancy, display name).
+constexpr int kNoScan = -1;  // scan of a family whose kernels have no SCAN parameter (the skip kernels)
+struct KernelRow {
+  const void* fn;
+  int threads;       // per block: 64, or 128 for the two-wave step kernel
+  const char* name;  // the kernel template, and its arguments (filled in by select_row):
+  int lt = 0, mode = 0, scan = 0;
+};
+// What a kernel unit exports: its row for a.L, a.mode and a.multi.  The step units
+// (td_step.hip, td_step_f16.hip) by kind: 0 large, 1 small, 2 small2 (StepArgs::small); the
+// frame-skip units (td_step_skip.hip, td_step_skip_f16.hip) and the partial-step units
+// (td_step_sel.hip, td_step_sel_f16.hip) have one kernel per row.
+KernelRow step_row_f32(const StepArgs& a, int kind);
+KernelRow step_row_f16(const StepArgs& a, int kind);
+KernelRow skip_row_f32(const StepArgs& a);
+KernelRow skip_row_f16(const StepArgs& a);
+KernelRow sel_row_f32(const StepArgs& a);
+KernelRow sel_row_f16(const StepArgs& a);
 
-// The step of a.small's kernel, or with reset = true the reset kernel (launch_reset).
-// ev0 / ev1: optional timing events bound to the step kernel's dispatch (td_kernel_timing).
-hipError_t launch_step(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-// Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute
-// units, for the one-wave (td_step_kernel_small) or two-wave (td_step_kernel_small2) build
-// of the observation format a.obs_f16.
-int step_resident_boards(const StepArgs& a, int cus, int waves);
-// The step kernel a.small selects for an aligned observation buffer, as a profiler prints
-// it (td_step_kernel_name): from the same table launch_step launches from (td_step_launch.h).
-std::string step_kernel_name(const StepArgs& a);
-// The same three for a float16 observation (a.obs_f16; called by the above; td_step_f16.hip).
-hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-int step_resident_boards_f16(const StepArgs& a, int cus, int waves);
-std::string step_kernel_name_f16(const StepArgs& a);
-// Frame skip (a.frame_skip > 1): a.frame_skip board steps per board in one launch of the
-// skip kernel of a.L, a.mode and a.obs_f16 (td_step_skip.hip, td_step_skip_f16.hip), and
-// that kernel's name as a profiler prints it.  Discrete actions, random_agent=True only.
-hipError_t launch_skip(const StepArgs& a, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-std::string skip_kernel_name(const StepArgs& a);
-hipError_t launch_skip_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-std::string skip_kernel_name_f16(const StepArgs& a);
-// Partial step (td_step_boards; td_step_sel.hip, td_step_sel_f16.hip): one env step for boards
-// ids[0 .. n), n >= 1, every other board left as it is; `ids` is device memory, the ids
-// validated by the caller.  One wave per list entry, the large kernel's shape, in the format
-// a.obs_f16; and that kernel's name as a profiler prints it.  frame_skip = 1 only.
-hipError_t launch_step_sel(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0 = nullptr,
-                           hipEvent_t ev1 = nullptr);
-std::string step_sel_kernel_name(const StepArgs& a);
-hipError_t launch_step_sel_f16(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1);
-std::string step_sel_kernel_name_f16(const StepArgs& a);
 // TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
 hipError_t launch_reset(const StepArgs& a, hipStream_t s);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),

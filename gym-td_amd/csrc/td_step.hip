@@ -1,6 +1,6 @@
 // td_step.hip -- the step kernels that write the float32 observation (td_step_kernel,
-// td_step_kernel_small, td_step_kernel_small2) with launch_step, step_resident_boards and
-// step_kernel_name.  The step itself is td_step_body.h; the float16 kernels are
+// td_step_kernel_small, td_step_kernel_small2) and their rows of the launch table
+// (step_row_f32).  The step itself is td_step_body.h; the float16 kernels are
 // td_step_f16.hip; the reset, refill and opponent kernels td_reset.hip.
 #include "td_kernels.h"
 #include "td_step_body.h"
@@ -38,20 +38,12 @@ __global__ __launch_bounds__(64) TD_SMALL_ATTR void td_step_kernel_small(StepArg
 // This unit's rows of the launch table (td_step_launch.h).
 template <int LT, int MODE, bool SCAN>
 struct F32Kernels {
-  static StepKernel large() { return {td_step_kernel<LT, MODE, SCAN>, 64, "td_step_kernel"}; }
-  static StepKernel small() { return {td_step_kernel_small<LT, MODE, SCAN>, 64, "td_step_kernel_small"}; }
-  static StepKernel small2() { return {td_step_kernel_small2<LT, MODE, SCAN>, 128, "td_step_kernel_small2"}; }
+  static KernelRow large() { return kernel_row(td_step_kernel<LT, MODE, SCAN>, 64, "td_step_kernel"); }
+  static KernelRow small() { return kernel_row(td_step_kernel_small<LT, MODE, SCAN>, 64, "td_step_kernel_small"); }
+  static KernelRow small2() { return kernel_row(td_step_kernel_small2<LT, MODE, SCAN>, 128, "td_step_kernel_small2"); }
 };
+static_assert(kObsUnitF32 == ObsFmt<float>::UB, "launch_step's alignment test goes by the float32 store unit");
 
-hipError_t launch_step(const StepArgs& a, hipStream_t s, bool reset, hipEvent_t ev0, hipEvent_t ev1) {
-  if (reset) return launch_reset(a, s);  // (the reset kernels branch on the format)
-  return a.obs_f16 ? launch_step_f16(a, s, ev0, ev1) : launch_step_kernel<F32Kernels, float>(a, s, ev0, ev1);
-}
-int step_resident_boards(const StepArgs& a, int cus, int waves) {
-  return a.obs_f16 ? step_resident_boards_f16(a, cus, waves) : step_kernel_resident<F32Kernels>(a, cus, waves);
-}
-std::string step_kernel_name(const StepArgs& a) {
-  return a.obs_f16 ? step_kernel_name_f16(a) : step_kernel_display_name<F32Kernels>(a);
-}
+KernelRow step_row_f32(const StepArgs& a, int kind) { return select_step_row<F32Kernels>(a, kind); }
 
 }  // namespace td

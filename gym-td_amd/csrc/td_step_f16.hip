@@ -1,7 +1,7 @@
 // td_step_f16.hip -- the step kernels that write a float16 observation (td_set_obs_format):
-// the _f16 variants of td_step.hip's three kernels (see there) with launch_step_f16,
-// step_resident_boards_f16 and step_kernel_name_f16.  A unit of its own, so that the two
-// formats compile beside each other, not one behind the other.
+// the _f16 variants of td_step.hip's three kernels (see there) and their rows of the launch
+// table (step_row_f16).  A unit of its own, so that the two formats compile beside each
+// other, not one behind the other.
 #include "td_kernels.h"
 #include "td_step_body.h"
 #include "td_step_launch.h"
@@ -29,15 +29,12 @@ __global__ __launch_bounds__(64) TD_SMALL_ATTR void td_step_kernel_small_f16(Ste
 // This unit's rows of the launch table (td_step_launch.h).
 template <int LT, int MODE, bool SCAN>
 struct F16Kernels {
-  static StepKernel large() { return {td_step_kernel_f16<LT, MODE, SCAN>, 64, "td_step_kernel_f16"}; }
-  static StepKernel small() { return {td_step_kernel_small_f16<LT, MODE, SCAN>, 64, "td_step_kernel_small_f16"}; }
-  static StepKernel small2() { return {td_step_kernel_small2_f16<LT, MODE, SCAN>, 128, "td_step_kernel_small2_f16"}; }
+  static KernelRow large() { return kernel_row(td_step_kernel_f16<LT, MODE, SCAN>, 64, "td_step_kernel_f16"); }
+  static KernelRow small() { return kernel_row(td_step_kernel_small_f16<LT, MODE, SCAN>, 64, "td_step_kernel_small_f16"); }
+  static KernelRow small2() { return kernel_row(td_step_kernel_small2_f16<LT, MODE, SCAN>, 128, "td_step_kernel_small2_f16"); }
 };
+static_assert(kObsUnitF16 == ObsFmt<_Float16>::UB, "launch_step's alignment test goes by the float16 store unit");
 
-hipError_t launch_step_f16(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  return launch_step_kernel<F16Kernels, _Float16>(a, s, ev0, ev1);
-}
-int step_resident_boards_f16(const StepArgs& a, int cus, int waves) { return step_kernel_resident<F16Kernels>(a, cus, waves); }
-std::string step_kernel_name_f16(const StepArgs& a) { return step_kernel_display_name<F16Kernels>(a); }
+KernelRow step_row_f16(const StepArgs& a, int kind) { return select_step_row<F16Kernels>(a, kind); }
 
 }  // namespace td

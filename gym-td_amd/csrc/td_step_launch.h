@@ -1,9 +1,11 @@
-// td_step_launch.h -- the host side of a step launch: one table of step kernels for both
-// observation formats.  What belongs here: with_side (a run-time map side as a template
-// argument, used by every launcher), the table row (StepKernel), its selection from a StepArgs,
-// and what is done with a row: launch it, ask its occupancy, print its name.  A step unit names
-// its kernels in a template K<LT, MODE, SCAN> with static large() / small() / small2() and
-// instantiates the functions below with it; a kernel is compiled where its address is taken.
+// td_step_launch.h -- the host side of a launch: one table for the step, frame-skip and
+// partial-step kernels of both observation formats.  What belongs here: with_side (a run-time
+// map side as a template argument, used by every launcher), the selection of a table row
+// (KernelRow, td_kernels.h) from a StepArgs, and what is done with a row: launch it, ask its
+// occupancy, print its name.  A kernel unit supplies only its row for <LT, MODE, SCAN>
+// (select_row) and exports that lookup; a kernel is compiled where its address is taken.  The
+// rest is ordinary host code, written once and called by td_capi.hip.  No device header is
+// included here.
 #pragma once
 #include <hip/hip_ext.h>
 
@@ -12,7 +14,6 @@
 #include <type_traits>
 
 #include "td_kernels.h"
-#include "td_step_obs.h"
 
 namespace td {
 
@@ -27,66 +28,111 @@ auto with_side(int L, F&& f) {
   }
 }
 
-struct StepKernel {
-  void (*fn)(StepArgs);
-  int threads;       // per board: 64, or 128 for the two-wave kernel
-  const char* name;  // the kernel template, and its arguments (filled in by step_kernel_row):
-  int lt = 0, mode = 0;
-  bool scan = false;
-};
-
-// kind: 0 large, 1 small, 2 small2 (StepArgs::small).  Generic L has the large kernel only.
-template <template <int, int, bool> class K, int LT, int MODE, bool SCAN>
-StepKernel step_kernel_row(int kind) {
-  StepKernel k = K<LT, MODE, SCAN>::large();
-  if constexpr (LT != 0) {
-    if (kind == 2) k = K<LT, MODE, SCAN>::small2();
-    else if (kind != 0) k = K<LT, MODE, SCAN>::small();
-  }
-  k.lt = LT; k.mode = MODE; k.scan = SCAN;
-  return k;
-}
-
-// The row of a.L, a.mode and a.multi (SCAN: the multi-action defender scan; TD-atk has none).
-template <template <int, int, bool> class K>
-StepKernel select_step_kernel(const StepArgs& a, int kind) {
-  return with_side(a.L, [&](auto side) {
-    constexpr int LT = decltype(side)::value;
-    if (a.mode == MODE_ATK) return step_kernel_row<K, LT, MODE_ATK, false>(kind);
-    if (a.mode == MODE_DEF) return a.multi ? step_kernel_row<K, LT, MODE_DEF, true>(kind) : step_kernel_row<K, LT, MODE_DEF, false>(kind);
-    return a.multi ? step_kernel_row<K, LT, MODE_2P, true>(kind) : step_kernel_row<K, LT, MODE_2P, false>(kind);
+// The row of a.L, a.mode and a.multi (SCAN: the multi-action defender scan; TD-atk has none):
+// row(lt, mode, scan), three std::integral_constant, returns the family's kernel of those
+// template arguments; lt / mode / scan of the row are filled in here.
+template <class F>
+KernelRow select_row(const StepArgs& a, F&& row) {
+  return with_side(a.L, [&](auto lt) {
+    auto r = [&](auto mode, auto scan) {
+      KernelRow k = row(lt, mode, scan);
+      k.lt = decltype(lt)::value;
+      k.mode = decltype(mode)::value;
+      if (k.scan != kNoScan) k.scan = decltype(scan)::value;
+      return k;
+    };
+    using Def = std::integral_constant<int, MODE_DEF>;
+    using Atk = std::integral_constant<int, MODE_ATK>;
+    using TwoP = std::integral_constant<int, MODE_2P>;
+    if (a.mode == MODE_ATK) return r(Atk{}, std::false_type{});
+    if (a.mode == MODE_DEF) return a.multi ? r(Def{}, std::true_type{}) : r(Def{}, std::false_type{});
+    return a.multi ? r(TwoP{}, std::true_type{}) : r(TwoP{}, std::false_type{});
   });
 }
 
-// Launches a.small's kernel, or the large kernel (its per-element path) where the observation
-// is not aligned to the format's store unit.  ev0 / ev1 (optional): timing events bound to the
-// step kernel's own dispatch (hipExtLaunchKernelGGL), so their interval is the kernel's
-// start-to-end as the dispatch packet timestamps it -- no marker packets around the launch.
-template <template <int, int, bool> class K, class OT>
-hipError_t launch_step_kernel(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  const bool aligned = (reinterpret_cast<uintptr_t>(a.obs) & (ObsFmt<OT>::UB - 1)) == 0;
-  const StepKernel k = select_step_kernel<K>(a, aligned ? a.small : 0);
-  if (ev0) hipExtLaunchKernelGGL(k.fn, dim3(a.B), dim3(k.threads), 0, s, ev0, ev1, 0, a);
-  else hipLaunchKernelGGL(k.fn, dim3(a.B), dim3(k.threads), 0, s, a);
+template <class... A>
+KernelRow kernel_row(void (*fn)(A...), int threads, const char* name, int scan = 0) {
+  return {reinterpret_cast<const void*>(fn), threads, name, 0, 0, scan};
+}
+
+// The step family's row.  A step unit names its kernels in a template K<LT, MODE, SCAN> with
+// static large() / small() / small2().  kind: 0 large, 1 small, 2 small2 (StepArgs::small);
+// generic L has the large kernel only.  (large, small2, small: the order in which the kernels
+// are named here is their order in the unit's code object, and a step kernel is about as large
+// as the instruction cache -- with another order the metric's kernel, the same instructions at
+// another address, ran 0.9 us of 164 longer, profiles/launch_table.)
+template <template <int, int, bool> class K>
+KernelRow select_step_row(const StepArgs& a, int kind) {
+  return select_row(a, [kind](auto lt, auto mode, auto scan) {
+    using T = K<decltype(lt)::value, decltype(mode)::value, decltype(scan)::value>;
+    KernelRow k = T::large();
+    if constexpr (decltype(lt)::value != 0) {
+      if (kind == 2) k = T::small2();
+      else if (kind != 0) k = T::small();
+    }
+    return k;
+  });
+}
+
+// The three families in the format a.obs_f16.
+inline KernelRow step_row(const StepArgs& a, int kind) { return a.obs_f16 ? step_row_f16(a, kind) : step_row_f32(a, kind); }
+inline KernelRow skip_row(const StepArgs& a) { return a.obs_f16 ? skip_row_f16(a) : skip_row_f32(a); }
+inline KernelRow sel_row(const StepArgs& a) { return a.obs_f16 ? sel_row_f16(a) : sel_row_f32(a); }
+
+// One block of k.threads per grid entry; args: the kernel's arguments, in order.  ev0 / ev1
+// (optional): timing events bound to the kernel's own dispatch (hipExtLaunchKernel), so their
+// interval is the kernel's start-to-end as the dispatch packet timestamps it -- no marker
+// packets around the launch (td_kernel_timing).
+inline hipError_t launch_row(const KernelRow& k, int grid, void** args, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  if (ev0) (void)hipExtLaunchKernel(k.fn, dim3(grid), dim3(k.threads), args, 0, s, ev0, ev1, 0);
+  else (void)hipLaunchKernel(k.fn, dim3(grid), dim3(k.threads), args, 0, s);
   return hipGetLastError();
 }
 
-// Step-kernel workgroups (boards) resident at once on the device: the batch size up to which
-// a step runs as one round of waves of the one-wave (waves = 1) or two-wave small-batch kernel.
-template <template <int, int, bool> class K>
-int step_kernel_resident(const StepArgs& a, int cus, int waves) {
-  const StepKernel k = select_step_kernel<K>(a, waves == 2 ? 2 : 1);
+// The observation's store unit per format (td_step_obs.h ObsFmt<OT>::UB; the step units assert it).
+constexpr int kObsUnitF32 = 16, kObsUnitF16 = 8;
+
+// The step of a.small's kernel, or of the large kernel (its per-element path) where the
+// observation is not aligned to the format's store unit.
+inline hipError_t launch_step(const StepArgs& a, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+  const uintptr_t unit = a.obs_f16 ? kObsUnitF16 : kObsUnitF32;
+  const bool aligned = (reinterpret_cast<uintptr_t>(a.obs) & (unit - 1)) == 0;
+  void* args[] = {const_cast<StepArgs*>(&a)};
+  return launch_row(step_row(a, aligned ? a.small : 0), a.B, args, s, ev0, ev1);
+}
+
+// Frame skip (a.frame_skip > 1): a.frame_skip board steps per board in one launch of the skip
+// kernel of a.L and a.mode.  Discrete actions, random_agent=True only.
+inline hipError_t launch_skip(const StepArgs& a, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+  void* args[] = {const_cast<StepArgs*>(&a)};
+  return launch_row(skip_row(a), a.B, args, s, ev0, ev1);
+}
+
+// Partial step (td_step_boards): one env step for boards ids[0 .. n), n >= 1, every other board
+// left as it is; `ids` is device memory, the ids validated by the caller.  One block per list
+// entry; the one kernel serves every alignment of the observation (step_board takes the
+// per-element writers where the buffer is not aligned for the format).  frame_skip = 1 only.
+inline hipError_t launch_step_sel(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0 = nullptr,
+                                  hipEvent_t ev1 = nullptr) {
+  void* args[] = {const_cast<StepArgs*>(&a), &ids, &n};
+  return launch_row(sel_row(a), n, args, s, ev0, ev1);
+}
+
+// Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute units:
+// the batch size up to which a step runs as one round of waves of the one-wave (waves = 1,
+// td_step_kernel_small) or two-wave (td_step_kernel_small2) kernel of the format a.obs_f16.
+inline int step_resident_boards(const StepArgs& a, int cus, int waves) {
+  const KernelRow k = step_row(a, waves == 2 ? 2 : 1);
   int n = 0;
   if (k.lt == 0) return 0;  // generic-L kernels: no small-batch build
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k.fn, k.threads, 0) == hipSuccess ? n * cus : 0;
 }
 
-// The kernel a.small selects, as a profiler prints it: "td_step_kernel_small2<20, 2, true>".
-template <template <int, int, bool> class K>
-std::string step_kernel_display_name(const StepArgs& a) {
-  const StepKernel k = select_step_kernel<K>(a, a.small);
+// A row as a profiler prints it: "td_step_kernel_small2<20, 2, true>", "td_skip_kernel<10, 0>".
+inline std::string kernel_display_name(const KernelRow& k) {
   char buf[96];
-  std::snprintf(buf, sizeof buf, "%s<%d, %d, %s>", k.name, k.lt, k.mode, k.scan ? "true" : "false");
+  if (k.scan == kNoScan) std::snprintf(buf, sizeof buf, "%s<%d, %d>", k.name, k.lt, k.mode);
+  else std::snprintf(buf, sizeof buf, "%s<%d, %d, %s>", k.name, k.lt, k.mode, k.scan ? "true" : "false");
   return buf;
 }
 

@@ -1,16 +1,14 @@
 // td_step_sel.h -- the partial step (td_step_boards): one wave per NAMED board, the boards
 // taken from a list.  What belongs here: the kernels' common body (step_sel_body: the large
 // kernel's body, td_step_body.h step_kernel_body with SMALL = false, with the board read from
-// the list) and the host side of their launch -- the table row (SelKernel), its selection from a
-// StepArgs as select_step_kernel selects a step kernel's, the launch and the profiler's name.
-// The kernels themselves are in td_step_sel.hip (float32 observation) and td_step_sel_f16.hip.
+// the list); device text only, the launch is td_step_launch.h's.  The kernels themselves are in
+// td_step_sel.hip (float32 observation) and td_step_sel_f16.hip.
 //
 // Nothing of a board that is not in the list is read or written: every access of step_board is
 // indexed by the board it is given, the observation writers store a board's own bytes of the
 // two lines it shares with its neighbours, and the episode statistics are accumulated per board.
 #pragma once
 #include "td_step_body.h"
-#include "td_step_launch.h"
 
 namespace td {
 
@@ -40,50 +38,6 @@ __device__ __forceinline__ void step_sel_body(const StepArgs& a, const int32_t* 
   store_cfg(S, cfgv, x.lane);  // (its load issued first: this wait leaves the board's loads in flight)
   wsync();  // every lane reads the block: no LDS access may move above its store
   step_board<NC, LT, MODE, SCAN, false, false, OT>(S, x, a, b, P);
-}
-
-struct SelKernel {
-  void (*fn)(StepArgs, const int32_t*, int);
-  const char* name;  // the kernel template, and its arguments (filled in by select_sel_kernel):
-  int lt = 0, mode = 0;
-  bool scan = false;
-};
-
-// The row of a.L, a.mode and a.multi: the five mode / scan rows of select_step_kernel.  A
-// unit names its kernels in a template K<LT, MODE, SCAN> with a static sel().
-template <template <int, int, bool> class K>
-SelKernel select_sel_kernel(const StepArgs& a) {
-  return with_side(a.L, [&](auto side) {
-    constexpr int LT = decltype(side)::value;
-    auto row = [](auto k, int mode, bool scan) {
-      SelKernel r = k;
-      r.lt = LT; r.mode = mode; r.scan = scan;
-      return r;
-    };
-    if (a.mode == MODE_ATK) return row(K<LT, MODE_ATK, false>::sel(), MODE_ATK, false);
-    if (a.mode == MODE_DEF)
-      return a.multi ? row(K<LT, MODE_DEF, true>::sel(), MODE_DEF, true) : row(K<LT, MODE_DEF, false>::sel(), MODE_DEF, false);
-    return a.multi ? row(K<LT, MODE_2P, true>::sel(), MODE_2P, true) : row(K<LT, MODE_2P, false>::sel(), MODE_2P, false);
-  });
-}
-
-// One block per list entry, n >= 1.  The one kernel serves every alignment of the observation
-// (step_board takes the per-element writers where the buffer is not aligned for the format).
-template <template <int, int, bool> class K>
-hipError_t launch_sel_kernel(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  const SelKernel k = select_sel_kernel<K>(a);
-  if (ev0) hipExtLaunchKernelGGL(k.fn, dim3(n), dim3(64), 0, s, ev0, ev1, 0, a, ids, n);
-  else hipLaunchKernelGGL(k.fn, dim3(n), dim3(64), 0, s, a, ids, n);
-  return hipGetLastError();
-}
-
-// As a profiler prints it: "td_step_sel_kernel<10, 0, false>".
-template <template <int, int, bool> class K>
-std::string sel_kernel_display_name(const StepArgs& a) {
-  const SelKernel k = select_sel_kernel<K>(a);
-  char buf[96];
-  std::snprintf(buf, sizeof buf, "%s<%d, %d, %s>", k.name, k.lt, k.mode, k.scan ? "true" : "false");
-  return buf;
 }
 
 }  // namespace td

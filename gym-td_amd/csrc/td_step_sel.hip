@@ -1,8 +1,9 @@
 // td_step_sel.hip -- the partial-step kernel that writes the float32 observation
-// (td_step_sel_kernel: td_step_boards) with launch_step_sel and step_sel_kernel_name.  The
+// (td_step_sel_kernel: td_step_boards) and its rows of the launch table (sel_row_f32).  The
 // body is td_step_sel.h, the step itself td_step_body.h; the float16 kernel is
 // td_step_sel_f16.hip.
 #include "td_kernels.h"
+#include "td_step_launch.h"
 #include "td_step_sel.h"
 
 namespace td {
@@ -14,16 +15,13 @@ __global__ __launch_bounds__(64) void td_step_sel_kernel(StepArgs a, const int32
   step_sel_body<LT, MODE, SCAN>(a, ids, n);
 }
 
-template <int LT, int MODE, bool SCAN>
-struct F32Sel {
-  static SelKernel sel() { return {td_step_sel_kernel<LT, MODE, SCAN>, "td_step_sel_kernel"}; }
-};
-
-hipError_t launch_step_sel(const StepArgs& a, const int32_t* ids, int n, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  return a.obs_f16 ? launch_step_sel_f16(a, ids, n, s, ev0, ev1) : launch_sel_kernel<F32Sel>(a, ids, n, s, ev0, ev1);
-}
-std::string step_sel_kernel_name(const StepArgs& a) {
-  return a.obs_f16 ? step_sel_kernel_name_f16(a) : sel_kernel_display_name<F32Sel>(a);
+// This unit's rows of the launch table (td_step_launch.h): the step kernels' five mode / scan
+// rows per side, no small-batch build.
+KernelRow sel_row_f32(const StepArgs& a) {
+  return select_row(a, [](auto lt, auto mode, auto scan) {
+    return kernel_row(td_step_sel_kernel<decltype(lt)::value, decltype(mode)::value, decltype(scan)::value>, 64,
+                      "td_step_sel_kernel");
+  });
 }
 
 }  // namespace td

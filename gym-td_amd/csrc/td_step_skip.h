@@ -17,20 +17,14 @@
 // kernel's refill rule per sub-step, so the stream's words, position and lazy-twist
 // boundary are those of k launches of td_step_kernel) and captured config blocks.
 //
-// What belongs here: skip_board (one board's macro step), the kernels' common body and the
-// host side of a launch (select / launch / name), instantiated per observation format by
-// td_step_skip.hip and td_step_skip_f16.hip.  The existing step kernels share no text with
+// What belongs here: skip_board (one board's macro step) and the kernels' common body,
+// instantiated per observation format by td_step_skip.hip and td_step_skip_f16.hip (device
+// text only: the launch is td_step_launch.h's).  The existing step kernels share no text with
 // this path beyond the pieces it calls (board_step, defender_op, attacker_actions,
 // opponent_*, enemy_stats, channel_scalars, reset_board, take_dry_ring, obs_dirty, the
 // observation writers): step_board is untouched.
 #pragma once
-#include <hip/hip_ext.h>
-
-#include <cstdio>
-#include <string>
-
 #include "td_step_body.h"
-#include "td_step_launch.h"
 
 namespace td {
 
@@ -235,43 +229,6 @@ __device__ __forceinline__ void skip_kernel_body(const StepArgs& a) {
   store_cfg(S, cfgv, x.lane);
   wsync();
   skip_board<NC, LT, MODE, OT>(S, raw, x, a, b, P);
-}
-
-// ---------------------------------------------------------------------------
-// host side: one kernel per (side, mode) and format; K<LT, MODE>::fn / ::name
-// ---------------------------------------------------------------------------
-struct SkipKernel {
-  void (*fn)(StepArgs);
-  const char* name;
-  int lt, mode;
-};
-
-template <template <int, int> class K>
-SkipKernel select_skip_kernel(const StepArgs& a) {
-  return with_side(a.L, [&](auto side) {
-    constexpr int LT = decltype(side)::value;
-    if (a.mode == MODE_ATK) return SkipKernel{K<LT, MODE_ATK>::fn(), K<LT, MODE_ATK>::name(), LT, MODE_ATK};
-    if (a.mode == MODE_DEF) return SkipKernel{K<LT, MODE_DEF>::fn(), K<LT, MODE_DEF>::name(), LT, MODE_DEF};
-    return SkipKernel{K<LT, MODE_2P>::fn(), K<LT, MODE_2P>::name(), LT, MODE_2P};
-  });
-}
-
-// ev0 / ev1 (optional): timing events bound to the kernel's own dispatch, as launch_step_kernel.
-template <template <int, int> class K>
-hipError_t launch_skip_kernel(const StepArgs& a, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
-  const SkipKernel k = select_skip_kernel<K>(a);
-  if (ev0) hipExtLaunchKernelGGL(k.fn, dim3(a.B), dim3(64), 0, s, ev0, ev1, 0, a);
-  else hipLaunchKernelGGL(k.fn, dim3(a.B), dim3(64), 0, s, a);
-  return hipGetLastError();
-}
-
-// As a profiler prints it: "td_skip_kernel<10, 0>".
-template <template <int, int> class K>
-std::string skip_kernel_display_name(const StepArgs& a) {
-  const SkipKernel k = select_skip_kernel<K>(a);
-  char buf[96];
-  std::snprintf(buf, sizeof buf, "%s<%d, %d>", k.name, k.lt, k.mode);
-  return buf;
 }
 
 }  // namespace td
