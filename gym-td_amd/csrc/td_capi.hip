@@ -23,9 +23,12 @@
 #include "../../include/td_diag.h"
 #include "td_copy_check.h"
 #include "td_ids_check.h"
+#include "td_kernel_choice.h"
 #include "td_kernels.h"
 #include "td_layout.h"
+#include "td_obs_ledger.h"
 #include "td_rng.h"
+#include "td_state_rec.h"
 #include "td_step_launch.h"
 
 using namespace td;
@@ -132,12 +135,7 @@ struct td_handle {
   int edge_wt = 2;  // observation lines shared with a neighbour: plain write-back stores, merged in the XCD's L2
                     // (1.088x vs 1.093x the algorithmic bytes at 65,536 boards, step time +-0, profiles/r04/s20);
                     // 1: write-through (sc1), the reference form of tests/test_gpu_store_policy.py
-  // td_retain_obs: the buffer the caller leaves to this handle's own writes, and whether it
-  // holds every board's observation as this handle's last write left it (obs_touch clears it)
-  const void* retained = nullptr;
-  bool retained_valid = false;     // every board's is known to be there
-  std::vector<uint8_t> obs_known;  // [B] board b's is (a reset into the buffer wrote it, or a step)
-  int n_known = 0;
+  ObsLedger ledger;  // td_retain_obs: the retained buffer and what is known of it (td_obs_ledger.h)
   // td_copy_boards, td_step_boards: the caller's id arrays travel through kIdSlots pinned slots of 2 B ids
   // in turn (allocated by td_create), each to d_pairs on the call's stream; a slot is
   // written again only once the event behind its last upload has passed (upload_ids)
@@ -229,48 +227,45 @@ std::unordered_map<const void*, Block> g_blocks;
 std::mutex g_handles_mu;
 std::unordered_set<td_handle*> g_handles;
 
-// Some board's observation would now differ from what the retained buffer holds, and
-// nothing wrote it there: the next step writes every byte (td_retain_obs).
-void obs_touch(td_handle* h) {
-  h->retained_valid = false;
-  if (h->n_known) std::fill(h->obs_known.begin(), h->obs_known.end(), (uint8_t)0);
-  h->n_known = 0;
-}
-// Board b's observation was just written whole into the retained buffer.
-void obs_mark(td_handle* h, int b) {
-  if (h->obs_known.size() != (size_t)h->B) h->obs_known.assign((size_t)h->B, 0);
-  if (!h->obs_known[(size_t)b]) {
-    h->obs_known[(size_t)b] = 1;
-    h->n_known += 1;
-  }
-  h->retained_valid = h->n_known == h->B;
-}
-// Every board's was (a step into the retained buffer).
-void obs_mark_all(td_handle* h) {
-  h->obs_known.assign((size_t)h->B, 1);
-  h->n_known = h->B;
-  h->retained_valid = true;
-}
-// A reset that writes into `obs`: the boards it resets are written whole.  Into the
-// retained buffer that keeps it current; anywhere else (or nowhere) leaves it behind.
-bool obs_reset_into(td_handle* h, const void* obs) {
-  const bool mine = obs && obs == h->retained;
-  if (!mine) obs_touch(h);
-  return mine;
-}
-// A call that returns early with an error leaves the retained buffer behind.
-struct ObsGuard {
-  td_handle* h;
-  bool ok = false;
-  ~ObsGuard() {
-    if (!ok) obs_touch(h);
-  }
+// The handle's device arrays, listed once: td_create allocates and zeroes them in this order,
+// td_destroy frees them, and td_create's failure message sums them.  bytes = B * per_board + fixed.
+struct DevArray {
+  void** slot;
+  size_t per_board, fixed;
 };
+#define TD_SLOT(m) reinterpret_cast<void**>(&h->m)
+std::vector<DevArray> dev_arrays(td_handle* h) {
+  const size_t w = sizeof(uint32_t);
+  return {{TD_SLOT(d_cfg), 0, NCFG * sizeof(TdDevCfg)},
+          {TD_SLOT(d_hdr), sizeof(TdHdr), 0},
+          {TD_SLOT(d_en_lp), ECAP * sizeof(double), 0},
+          {TD_SLOT(d_en_mg), ECAP * sizeof(double), 0},
+          {TD_SLOT(d_en_inf), ECAP * w, 0},
+          {TD_SLOT(d_tw_cd), TCAP * sizeof(double), 0},
+          {TD_SLOT(d_tw_inf), TCAP * w, 0},
+          {TD_SLOT(d_cells), (size_t)h->NC * w, 0},
+          {TD_SLOT(d_opp), OPP_WORDS * w, 0},
+          {TD_SLOT(d_hot), HOT_WORDS * w, 0},
+          {TD_SLOT(d_np), OPP_WORDS * w, 0},
+          {TD_SLOT(d_nxt), (size_t)NSLOT * slot_words(h->L) * w, 0},
+          {TD_SLOT(d_lay_head), w, 0},
+          {TD_SLOT(d_lay_tail), w, 0},
+          {TD_SLOT(d_lay_claim), w, 0},
+          {TD_SLOT(d_ovr_idx), sizeof(int32_t), 0},
+          {TD_SLOT(d_scratch), h->scratch_stride, 0},
+          {TD_SLOT(d_mask), 1, 0},
+          {TD_SLOT(d_fail), 1, 0},
+          {TD_SLOT(d_stage), 0, (size_t)h->stage_cap * h->lw * w},
+          {TD_SLOT(d_epstats), 0, 2 * sizeof(double)},
+          {TD_SLOT(d_lastep), sizeof(td_episode_record), 0},
+          {TD_SLOT(d_guard_to), 0, w},
+          {TD_SLOT(d_pairs), 2 * sizeof(int32_t), 0}};
+}
+#undef TD_SLOT
 
-template <class T>
-int dalloc(T** p, size_t n) {
-  HIP_OK(hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
-  HIP_OK(hipMemset(*p, 0, std::max<size_t>(n, 1) * sizeof(T)));
+int dalloc(void** p, size_t bytes) {
+  HIP_OK(hipMalloc(p, std::max<size_t>(bytes, 1)));
+  HIP_OK(hipMemset(*p, 0, std::max<size_t>(bytes, 1)));
   return 0;
 }
 
@@ -312,16 +307,11 @@ void parallel_for(int n, F fn) {
   for (auto& t : pool) t.join();
 }
 
-// The step kernel (td_set_step_kernel): small = 0 large, 1 small, 2 small2.  Write-through
-// observation stores go with the small kernels where the batch's observation fits the
-// 256-MiB Infinity Cache (scripts/storepol.hip: 21.8 vs 30.0 us at 8,192 boards).
+// The step kernel (td_set_step_kernel): small = 0 large, 1 small, 2 small2, and whether its
+// observation stores are write-through (td_kernel_choice.h obs_write_through).
 int apply_kernel(td_handle* h, int small) {
   h->small = small;
-  const bool f16 = h->obs_fmt == TD_OBS_F16;
-  const double obs_bytes = (double)h->B * NCH * h->NC * (f16 ? 2.0 : 4.0);
-  // (Write-through beyond the Infinity Cache -- any kernel, TD_OBS_WT=1 -- measured 1.5-1.7x
-  // slower steps at 16,384-65,536 boards, profiles/r03/s21.)
-  h->obs_wt = h->small && obs_bytes <= 192.0 * 1024 * 1024 ? 1 : 0;
+  h->obs_wt = obs_write_through(small, h->L, h->obs_fmt, h->B);
   // (while frame skip is on, td_step launches the skip kernel whatever kind is kept here)
   // (for an aligned observation buffer: launch_step takes the large kernel for any other)
   const StepArgs a = base_args(h);
@@ -329,37 +319,10 @@ int apply_kernel(td_handle* h, int small) {
   return 0;
 }
 
-// TD_KERNEL_AUTO: the small-batch kernel where the whole batch is one round of waves,
-// two waves per board up to half a round -- and again over a few rounds, where the
-// second wave's half of the observation shortens every board's step more than the
-// halved residency costs (single-action boards, profiles/r03/s7, same box: 10x10
-// 12,288 / 16,384 boards 237.8 / 255.4 vs 224.0 / 238.5 M env-steps/s with the large
-// kernel, 32,768 a tie; 30x30 16,384 / 32,768 boards 30.8 / 31.9 vs 29.8 / 31.2 M, 65,536
-// 30.0 vs 30.2 M; TD-2p 20x20 multi-action at 16,384: 48.0 vs 51.5 M in round 3, 54.0 vs
-// 52.1 M on the round-4 build, r04/s10).
-// td_set_step_kernel overrides.
+// TD_KERNEL_AUTO (td_kernel_choice.h auto_kernel_kind); td_set_step_kernel overrides.
 int auto_kernel(const td_handle* h) {
-  const bool f16 = h->obs_fmt == TD_OBS_F16;
-  const int resident = h->resident[f16][0], resident2 = h->resident[f16][1];
-  // two-wave kernel up to this many rounds (TD-2p 20x20 multi-action at 16,384 boards:
-  // 303.3-303.6 vs 314-315 us per step with the large kernel, profiles/r04/s10; TD-def
-  // 10x10 at every batch above one round since round 5: 32,768 / 49,152 / 65,536 boards
-  // 107.5-107.9 / 156.5-156.8 / 203.4-204.1 vs 111.7-111.9 / 160.6-160.9 / 208.2-208.4 us,
-  // profiles/r05/s33, s34)
-  const int rounds2 = h->multi ? (h->L == 20 && h->mode == TD_MODE_2P ? 8 : 0)
-                               : h->L == 10 ? (h->mode == TD_MODE_DEF ? (1 << 20) : 3) : h->L == 30 ? 10 : 0;
-  // The float16 observation at 10x10: the one-wave small kernel at every batch above half a
-  // round.  With half the bytes to store the step is bound by the boards in flight, not by
-  // the store stream, and the second wave halves them (TD-def 12,288 / 16,384 / 32,768 /
-  // 65,536 boards: 38.9 / 47.5 / 82.7 / 158.4 us per step against 45.2 / 57.1 / 103.4 /
-  // 201.1 two-wave and 39.3 / 49.2 / 88.8 / 172.0 large; TD-atk at 16,384 and TD-2p at
-  // 32,768 alike, profiles/obs_f16/f16_sizes.jsonl).  At 20x20 and 30x30 the three kernels
-  // are within 1-3 % of each other in float16, the float32 rule's choice never the slowest.
-  if (f16 && h->L == 10) return h->B <= resident2 ? 2 : 1;
-  return h->B <= resident2                                  ? 2
-         : h->B <= resident                                 ? 1
-         : (int64_t)h->B <= (int64_t)rounds2 * resident     ? 2
-                                                            : 0;
+  const int* r = h->resident[h->obs_fmt == TD_OBS_F16];
+  return auto_kernel_kind(h->L, h->mode, h->multi, h->obs_fmt, h->B, r[0], r[1]);
 }
 
 // Drop staged layouts: they were drawn from a stream that has been replaced.
@@ -450,6 +413,14 @@ int upload_ids(td_handle* h, const int32_t* ids0, const int32_t* ids1, int n, hi
   return 0;
 }
 
+// td_create gives up: the handle goes, the message stays.
+td_handle* create_failed(td_handle* h) {
+  std::string e = g_err;
+  td_destroy(h);
+  g_err = e;
+  return nullptr;
+}
+
 }  // namespace
 
 extern "C" {
@@ -492,14 +463,7 @@ int td_free_device(void* p) {
   }
   {  // a later allocation may reuse the address: no handle may take it for the buffer it retained
     std::lock_guard<std::mutex> g(g_handles_mu);
-    const char* lo = static_cast<const char*>(p);
-    for (td_handle* h : g_handles) {
-      const char* r = static_cast<const char*>(h->retained);
-      if (r && r >= lo && r < lo + std::max<size_t>(bytes, 1)) {
-        h->retained = nullptr;
-        obs_touch(h);
-      }
-    }
+    for (td_handle* h : g_handles) h->ledger.freed(p, bytes);
   }
   HIP_OK(hipFree(p));
   return 0;
@@ -584,43 +548,21 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
   td_handle* h = new td_handle();
   h->L = map_size; h->NC = map_size * map_size; h->B = n_boards; h->mode = mode; h->multi = multi_action ? 1 : 0;
   h->difficulty = difficulty; h->device = device; h->lw = layout_words(map_size);
+  h->ledger.B = n_boards;
   h->scratch_stride = (sizeof(RoadResume) + road_scratch_bytes(map_size) + 15) & ~(size_t)15;
   h->stage_cap = std::min(n_boards, 4096);
   build_dev_cfg(*cfg, h->dcfg);
   const size_t B = (size_t)n_boards;
   int rc = 0;
-  rc |= dalloc(&h->d_cfg, NCFG);
-  rc |= dalloc(&h->d_hdr, B);
-  rc |= dalloc(&h->d_en_lp, B * ECAP);
-  rc |= dalloc(&h->d_en_mg, B * ECAP);
-  rc |= dalloc(&h->d_en_inf, B * ECAP);
-  rc |= dalloc(&h->d_tw_cd, B * TCAP);
-  rc |= dalloc(&h->d_tw_inf, B * TCAP);
-  rc |= dalloc(&h->d_cells, B * h->NC);
-  rc |= dalloc(&h->d_opp, B * OPP_WORDS);
-  rc |= dalloc(&h->d_hot, B * HOT_WORDS);
-  rc |= dalloc(&h->d_np, B * OPP_WORDS);
-  rc |= dalloc(&h->d_nxt, (size_t)B * NSLOT * slot_words(map_size));
-  rc |= dalloc(&h->d_lay_head, B);
-  rc |= dalloc(&h->d_lay_tail, B);
-  rc |= dalloc(&h->d_lay_claim, B);
-  rc |= dalloc(&h->d_ovr_idx, B);
-  rc |= dalloc(&h->d_scratch, B * h->scratch_stride);
-  rc |= dalloc(&h->d_mask, B);
-  rc |= dalloc(&h->d_fail, B);
-  rc |= dalloc(&h->d_stage, (size_t)h->stage_cap * h->lw);
-  rc |= dalloc(&h->d_epstats, 2);
-  rc |= dalloc(&h->d_lastep, B);
-  rc |= dalloc(&h->d_guard_to, 1);
-  rc |= dalloc(&h->d_pairs, 2 * B);
+  for (const DevArray& a : dev_arrays(h)) rc |= dalloc(a.slot, B * a.per_board + a.fixed);
   if (!rc && hipHostMalloc((void**)&h->id_stage, kIdSlots * 2 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
     rc = fail("td_create: %zu B of pinned host memory (td_copy_boards' index slots)", kIdSlots * 2 * B * sizeof(int32_t));
   for (int q = 0; q < kIdSlots && !rc; ++q)
     if (hipEventCreateWithFlags(&h->id_ev[q], hipEventDisableTiming) != hipSuccess) rc = fail("event");
   if (rc) {  // name the footprint (the staged-layout rings are most of it at large L)
     const double ring = (double)B * NSLOT * slot_words(map_size) * 4.0;
-    const double total = (double)B * (sizeof(TdHdr) + ECAP * 20 + TCAP * 12 + (size_t)h->NC * 4 + 2 * OPP_WORDS * 4 +
-                                      HOT_WORDS * 4 + 12 + h->scratch_stride + 2 + sizeof(td_episode_record)) + ring;
+    double total = 0.0;  // everything asked for, the rings included
+    for (const DevArray& a : dev_arrays(h)) total += (double)(B * a.per_board + a.fixed);
     std::string e = g_err;
     fail("td_create: %d boards at L = %d need %.1f MB of device memory (%.1f MB of it the staged-layout rings, "
          "%d x %d words per board): %s", n_boards, map_size, total / 1e6, ring / 1e6, NSLOT, slot_words(map_size),
@@ -646,7 +588,7 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
     const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
     if (!rc && hipEventCreateWithFlags(&h->ev_step, fl) != hipSuccess) rc = fail("event");
   }
-  if (rc) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
+  if (rc) return create_failed(h);
   {  // boards resident at once, per format and kernel: what TD_KERNEL_AUTO goes by (auto_kernel)
     int cus = 0;
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
@@ -656,11 +598,11 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
       h->resident[f][0] = step_resident_boards(ra, cus, 1);
       h->resident[f][1] = step_resident_boards(ra, cus, 2);
     }
-    if (apply_kernel(h, auto_kernel(h))) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
+    if (apply_kernel(h, auto_kernel(h))) return create_failed(h);
   }
   std::vector<uint32_t> seeds(B);
   for (size_t b = 0; b < B; ++b) seeds[b] = (uint32_t)b;
-  if (td_seed(h, seeds.data(), seeds.data()) != 0) { std::string e = g_err; td_destroy(h); g_err = e; return nullptr; }
+  if (td_seed(h, seeds.data(), seeds.data()) != 0) return create_failed(h);
   {
     std::lock_guard<std::mutex> g(g_handles_mu);
     g_handles.insert(h);
@@ -676,13 +618,8 @@ void td_destroy(td_handle* h) {
   }
   (void)hipSetDevice(h->device);
   (void)hipDeviceSynchronize();
-  void* dptrs[] = {h->d_cfg, h->d_hdr, h->d_en_lp, h->d_en_mg, h->d_en_inf, h->d_tw_cd, h->d_tw_inf,
-                   h->d_cells, h->d_opp, h->d_hot, h->d_np, h->d_nxt, h->d_scratch, h->d_lay_head, h->d_lay_tail,
-                   h->d_lay_claim, h->d_ovr_idx, h->d_mask, h->d_fail, h->d_stage, h->d_epstats, h->d_lastep,
-                   h->d_guard_to};
-  for (void* p : dptrs)
-    if (p) (void)hipFree(p);
-  if (h->d_pairs) (void)hipFree(h->d_pairs);
+  for (const DevArray& a : dev_arrays(h))
+    if (*a.slot) (void)hipFree(*a.slot);
   if (h->id_stage) (void)hipHostFree(h->id_stage);
   for (hipEvent_t e : h->id_ev)
     if (e) (void)hipEventDestroy(e);
@@ -726,7 +663,7 @@ int td_set_config(td_handle* h, const td_config* cfg) {
   HIP_OK(hipMemcpy(h->d_cfg + slot, &d, sizeof d, hipMemcpyHostToDevice));
   h->dcfg = d;
   h->epoch = slot;
-  obs_touch(h);  // channels 21-24 and 41-44 read the current block
+  h->ledger.touch();  // channels 21-24 and 41-44 read the current block
   return 0;
 }
 
@@ -850,8 +787,8 @@ int td_reset(td_handle* h, const uint8_t* host_mask, float* obs, void* stream) {
   std::vector<uint8_t> mask((size_t)h->B, 1);
   if (host_mask) std::memcpy(mask.data(), host_mask, (size_t)h->B);
   HIP_OK(hipDeviceSynchronize());
-  const bool mine = obs_reset_into(h, obs);
-  ObsGuard guard{h};
+  const bool mine = h->ledger.reset_into(obs);
+  ObsLedger::Guard guard{&h->ledger};
   if (run_reset(h, mask, obs, s)) return -1;
   std::vector<uint8_t> fl((size_t)h->B);
   HIP_OK(hipMemcpy(fl.data(), h->d_fail, (size_t)h->B, hipMemcpyDeviceToHost));
@@ -859,7 +796,7 @@ int td_reset(td_handle* h, const uint8_t* host_mask, float* obs, void* stream) {
   for (int b = 0; b < h->B; ++b) {
     if (!mask[(size_t)b]) continue;
     if (fl[(size_t)b]) h->last_reset_failed.push_back(b);
-    else if (mine) obs_mark(h, b);  // (a board whose draw failed keeps its state, and its observation)
+    else if (mine) h->ledger.mark(b);  // (a board whose draw failed keeps its state, and its observation)
   }
   guard.ok = true;
   return (int)h->last_reset_failed.size();
@@ -887,8 +824,8 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
                   "a road has at most %d cells)", i, r[1], r[3], MAX_ROAD_CELLS - 1, MAX_ROAD_CELLS);
   }
   HIP_OK(hipDeviceSynchronize());
-  const bool mine = n > 0 && obs_reset_into(h, obs);
-  ObsGuard guard{h};
+  const bool mine = n > 0 && h->ledger.reset_into(obs);
+  ObsLedger::Guard guard{&h->ledger};
   std::vector<int32_t> idx((size_t)h->B, -1);
   for (int i0 = 0; i0 < n; i0 += h->stage_cap) {
     const int m = std::min(h->stage_cap, n - i0);
@@ -907,7 +844,7 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
     HIP_OK(launch_reset(a, s));
     h->since_guard = kGuardEvery;
     HIP_OK(hipStreamSynchronize(s));
-    for (int i = 0; mine && i < m; ++i) obs_mark(h, boards[i0 + i]);
+    for (int i = 0; mine && i < m; ++i) h->ledger.mark(boards[i0 + i]);
   }
   guard.ok = true;
   return 0;
@@ -924,14 +861,14 @@ int td_copy_boards(td_handle* h, const int32_t* src, const int32_t* dst, int n, 
   hipStream_t s = (hipStream_t)stream;
   // the destinations' states change: rows written into the retained buffer keep it current,
   // any other buffer (or none) leaves it behind
-  const bool mine = obs_reset_into(h, obs);
-  ObsGuard guard{h};
+  const bool mine = h->ledger.reset_into(obs);
+  ObsLedger::Guard guard{&h->ledger};
   if (upload_ids(h, src, dst, n, s)) return -1;
   StepArgs a = base_args(h);
   a.obs = obs;
   const EvPair ev = next_timing_pair(h);  // a copy kernel's dispatch is timed too, whatever `every` is
   HIP_OK(launch_copy(a, h->d_pairs, n, s, ev.e0, ev.e1));
-  for (int i = 0; mine && i < n; ++i) obs_mark(h, dst[i]);  // (a destination without an episode is written whole by its next step)
+  for (int i = 0; mine && i < n; ++i) h->ledger.mark(dst[i]);  // (a destination without an episode is written whole by its next step)
   guard.ok = true;
   return 0;
 }
@@ -994,9 +931,9 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   StepArgs a = step_args(h, io);
   // td_retain_obs: a step into the retained buffer may skip what the buffer already holds;
   // any other step writes every byte and leaves the retained buffer behind.
-  const bool retained = h->retained && (const void*)io->obs == h->retained;
-  a.obs_skip = retained && h->retained_valid ? 1 : 0;
-  ObsGuard guard{h};
+  const bool retained = h->ledger.is_retained(io->obs);
+  a.obs_skip = h->ledger.full_step_skips(io->obs) ? 1 : 0;
+  ObsLedger::Guard guard{&h->ledger};
   if (before_step_launch(h, a, s)) return -1;
   const EvPair ev = (h->steps - h->tev_from) % h->tev_every == 0 ? next_timing_pair(h) : EvPair{};
   // frame skip: one launch of the skip kernel runs the k board steps (td_step_skip.h).  The refill
@@ -1005,8 +942,8 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   if (h->autoreset && h->opp_np) HIP_OK(launch_autoreset(a, s));
   h->steps += 1;
   h->since_guard += 1;
-  if (!retained) obs_touch(h);
-  else if (!h->retained_valid) obs_mark_all(h);  // every board's observation is in the retained buffer now
+  if (!retained) h->ledger.touch();
+  else if (!a.obs_skip) h->ledger.mark_all();  // every board's observation is in the retained buffer now
   guard.ok = true;
   return 0;
 }
@@ -1030,20 +967,19 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
   StepArgs a = step_args(h, io);
   // td_retain_obs: a step into the retained buffer may skip what the buffer already holds of
   // the boards it steps; into any other buffer it leaves the retained buffer behind.
-  const bool retained = h->retained && (const void*)io->obs == h->retained;
-  bool known = retained && (h->retained_valid || h->obs_known.size() == (size_t)h->B);
-  for (int i = 0; known && !h->retained_valid && i < n; ++i) known = h->obs_known[(size_t)boards[i]] != 0;
+  const bool retained = h->ledger.is_retained(io->obs);
+  const bool known = h->ledger.partial_step_skips(io->obs, boards, n);
   a.obs_skip = known ? 1 : 0;
-  ObsGuard guard{h};
+  ObsLedger::Guard guard{&h->ledger};
   // on the stream: the refill and the ring guard, then the ids, then the kernel
   if (before_step_launch(h, a, s) || upload_ids(h, boards, nullptr, n, s)) return -1;
   const EvPair ev = next_timing_pair(h);  // whatever `every` is (as the copy's)
   HIP_OK(launch_step_sel(a, h->d_pairs, n, s, ev.e0, ev.e1));
   h->steps += 1;
   h->since_guard += 1;
-  if (!retained) obs_touch(h);
+  if (!retained) h->ledger.touch();
   else
-    for (int i = 0; !known && i < n; ++i) obs_mark(h, boards[i]);  // written whole just now
+    for (int i = 0; !known && i < n; ++i) h->ledger.mark(boards[i]);  // written whole just now
   guard.ok = true;
   return 0;
 }
@@ -1109,7 +1045,7 @@ int td_set_obs_format(td_handle* h, int fmt) {
   if (fmt != TD_OBS_F32 && fmt != TD_OBS_F16) return fail("td_set_obs_format: unknown format %d (TD_OBS_F32 = 0, TD_OBS_F16 = 1)", fmt);
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep the format they were enqueued with
   h->obs_fmt = fmt;
-  obs_touch(h);  // (the same format again too: the caller may have changed the buffer's element)
+  h->ledger.touch();  // (the same format again too: the caller may have changed the buffer's element)
   return apply_kernel(h, h->kernel_forced ? h->small : auto_kernel(h));
 }
 
@@ -1137,12 +1073,12 @@ size_t td_obs_bytes(td_handle* h) {
 int td_retain_obs(td_handle* h, const void* obs) {
   if (!h) return fail("NULL handle");
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep what they were enqueued with
-  h->retained = obs;
-  obs_touch(h);  // nothing is known of the buffer yet: the next step into it writes every byte
+  h->ledger.retained = obs;
+  h->ledger.touch();  // nothing is known of the buffer yet: the next step into it writes every byte
   return 0;
 }
 
-const void* td_retained_obs(td_handle* h) { return h ? h->retained : nullptr; }
+const void* td_retained_obs(td_handle* h) { return h ? h->ledger.retained : nullptr; }
 
 const char* td_step_kernel_name(td_handle* h) { return h ? h->kernel_name.c_str() : ""; }
 
@@ -1204,7 +1140,7 @@ int td_opponent(td_handle* h, int side, int level, const uint8_t* host_mask, voi
   HIP_OK(hipMemcpy(h->d_mask, mask.data(), (size_t)h->B, hipMemcpyHostToDevice));
   StepArgs a = base_args(h);
   a.reset_mask = h->d_mask;
-  obs_touch(h);  // enemies, towers and costs change; no observation is written
+  h->ledger.touch();  // enemies, towers and costs change; no observation is written
   HIP_OK(launch_opponent(a, side, level, s));
   HIP_OK(hipStreamSynchronize(s));
   return 0;
@@ -1232,87 +1168,51 @@ int td_layout_generate(uint32_t* np_state625, int map_size, int max_attempts, ui
 
 size_t td_state_bytes(td_handle* h, int count) {
   if (!h || count < 0) return 0;
-  return (size_t)count * (sizeof(TdHdr) + ECAP * (8 + 8 + 4) + TCAP * (8 + 4) + (size_t)h->NC * 4 + OPP_WORDS * 4);
+  return state_rec_bytes(h->NC, (size_t)count);
 }
 
+// The record (td_state_rec.h) to or from the boards [b0, b0 + count): one copy per record array.
 static int state_copy(td_handle* h, int b0, int count, void* host, bool to_host) {
   if (!h || b0 < 0 || count < 0 || b0 + count > h->B) return fail("state copy: bad board range");
   HIP_OK(hipDeviceSynchronize());
   uint8_t* p = (uint8_t*)host;
-  auto cp = [&](void* dev, size_t elem) -> int {
-    size_t bytes = (size_t)count * elem;
-    uint8_t* d = (uint8_t*)dev + (size_t)b0 * elem;
-    HIP_OK(hipMemcpy(to_host ? (void*)p : (void*)d, to_host ? (void*)d : (void*)p, bytes,
-                     to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice));
-    p += bytes;
-    return 0;
-  };
-  uint32_t* opp = (uint32_t*)(p + (size_t)count * (sizeof(TdHdr) + ECAP * 20 + TCAP * 12 + (size_t)h->NC * 4));
   std::vector<uint8_t> retagged;
-  if (!to_host) {
-    // imported enemies and towers take the current config epoch: epoch tags of another
-    // engine (or of blocks since recycled) mean nothing here
-    retagged.assign(p, p + td_state_bytes(h, count));
-    uint8_t* q = retagged.data();
-    uint32_t* einf = (uint32_t*)(q + (size_t)count * (sizeof(TdHdr) + ECAP * 16));
-    uint32_t* tinf = (uint32_t*)(q + (size_t)count * (sizeof(TdHdr) + ECAP * 20 + TCAP * 8));
-    for (size_t i = 0; i < (size_t)count * ECAP; ++i) einf[i] = (einf[i] & 0x00ffffffu) | ((uint32_t)h->epoch << 24);
-    for (size_t i = 0; i < (size_t)count * TCAP; ++i)
-      tinf[i] = (tinf[i] & 0x0000ffffu) | ((uint32_t)h->epoch << 16) | ((uint32_t)h->epoch << 24);
-    // cell words: bits 10-15 are not part of the layout format (the step keeps the tower of a
-    // cell there in LDS only)
-    uint32_t* cw = (uint32_t*)(q + (size_t)count * (sizeof(TdHdr) + ECAP * 20 + TCAP * 12));
-    for (size_t i = 0; i < (size_t)count * h->NC; ++i) cw[i] &= ~(0x3Fu << 10);
-    p = q;
-    opp = (uint32_t*)(p + (size_t)count * (sizeof(TdHdr) + ECAP * 20 + TCAP * 12 + (size_t)h->NC * 4));
+  if (!to_host) {  // the caller's record stays as it is: a copy takes the current config epoch
+    retagged.assign(p, p + state_rec_bytes(h->NC, (size_t)count));
+    p = retagged.data();
+    state_rec_retag(p, h->NC, (size_t)count, h->epoch);
   }
+  uint32_t* opp = (uint32_t*)(p + state_rec_offset(SR_OPP_MT, h->NC, (size_t)count));
   std::vector<uint32_t> hot((size_t)count * HOT_WORDS);
   if (!to_host) {  // the hot record follows the imported words (no pre-drawn outputs)
-    for (int i = 0; i < count; ++i) {
-      hot[(size_t)i * HOT_WORDS] = opp[(size_t)i * OPP_WORDS + MT_N];
-      hot[(size_t)i * HOT_WORDS + 1] = opp[(size_t)i * OPP_WORDS + MT_N + 1];
-    }
+    state_rec_pos_to_hot(opp, hot.data(), HOT_WORDS, (size_t)count);
     HIP_OK(hipMemcpy(h->d_hot + (size_t)b0 * HOT_WORDS, hot.data(), hot.size() * 4, hipMemcpyHostToDevice));
   }
-  if (cp(h->d_hdr, sizeof(TdHdr)) || cp(h->d_en_lp, ECAP * 8) || cp(h->d_en_mg, ECAP * 8) ||
-      cp(h->d_en_inf, ECAP * 4) || cp(h->d_tw_cd, TCAP * 8) || cp(h->d_tw_inf, TCAP * 4) ||
-      cp(h->d_cells, (size_t)h->NC * 4) || cp(h->d_opp, OPP_WORDS * 4))
-    return -1;
+  void* const dev[SR_ARRAYS] = {h->d_hdr,   h->d_en_lp,  h->d_en_mg, h->d_en_inf,
+                                h->d_tw_cd, h->d_tw_inf, h->d_cells, h->d_opp};  // in record order
+  for (int k = 0; k < SR_ARRAYS; ++k) {
+    const size_t elem = state_rec_elem(k, h->NC), bytes = (size_t)count * elem;
+    uint8_t* d = (uint8_t*)dev[k] + (size_t)b0 * elem;
+    uint8_t* r = p + state_rec_offset(k, h->NC, (size_t)count);
+    HIP_OK(hipMemcpy(to_host ? (void*)r : (void*)d, to_host ? (void*)d : (void*)r, bytes,
+                     to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice));
+  }
   if (to_host) {  // position and lazy boundary live in the hot record
     HIP_OK(hipMemcpy(hot.data(), h->d_hot + (size_t)b0 * HOT_WORDS, hot.size() * 4, hipMemcpyDeviceToHost));
-    for (int i = 0; i < count; ++i) {
-      opp[(size_t)i * OPP_WORDS + MT_N] = hot[(size_t)i * HOT_WORDS];
-      opp[(size_t)i * OPP_WORDS + MT_N + 1] = hot[(size_t)i * HOT_WORDS + 1];
-    }
+    state_rec_pos_from_hot(opp, hot.data(), HOT_WORDS, (size_t)count);
   }
   return 0;
 }
 
 int td_export_state(td_handle* h, int b0, int count, void* host_dst) { return state_copy(h, b0, count, host_dst, true); }
 
-// A record whose board has a layout must carry the captured max_cost / max_base_LP the
-// step divides by (TdHdr.format: header format 2); a record of another format, or a
-// hand-built one with zeros there, would silently clamp every cost to 0 and divide the
-// observation's scalar channels by zero.
+// The headers are checked before anything is copied (td_state_rec.h state_rec_check).
 int td_import_state(td_handle* h, int b0, int count, const void* host_src) {
   if (!h || !host_src || b0 < 0 || count < 0 || b0 + count > h->B) return fail("td_import_state: bad arguments");
-  const TdHdr* hdr = static_cast<const TdHdr*>(host_src);
-  for (int i = 0; i < count; ++i) {
-    const TdHdr& x = hdr[i];
-    if (x.num_roads < 1 || x.num_roads > 3) continue;  // a board never reset: nothing is stepped
-    if (x.format != kHdrFormat)
-      return fail("td_import_state: board %d: header format 0x%x, expected 0x%x (a record of another build?)",
-                  b0 + i, (unsigned)x.format, (unsigned)kHdrFormat);
-    if (!(x.max_cost > 0.0) || x.max_base_LP < 1)
-      return fail("td_import_state: board %d: max_cost %g / max_base_LP %d (must be > 0 / >= 1)", b0 + i, x.max_cost,
-                  x.max_base_LP);
-    if (x.n_en < 0 || x.n_en > ECAP || x.n_tw < 0 || x.n_tw > TCAP)
-      return fail("td_import_state: board %d: %d enemies / %d towers exceed the capacity", b0 + i, x.n_en, x.n_tw);
-    if (x.maxdist < 0 || x.maxdist > MAX_ROAD_CELLS - 1)
-      return fail("td_import_state: board %d: max dist %d (must be 0..%d: a road has at most %d cells)", b0 + i,
-                  x.maxdist, MAX_ROAD_CELLS - 1, MAX_ROAD_CELLS);
-  }
-  obs_touch(h);
+  char msg[200];
+  if (state_rec_check(static_cast<const TdHdr*>(host_src), count, b0, msg, sizeof msg))
+    return fail("td_import_state: %s", msg);
+  h->ledger.touch();
   return state_copy(h, b0, count, const_cast<void*>(host_src), false);
 }
 

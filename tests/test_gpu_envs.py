@@ -344,6 +344,14 @@ def test_export_import_roundtrip():
     finally:
         a_eng.close()
         b_eng.close()
+    # the record's size as the library states it is what the Python mirror of its layout encodes
+    from gym_TD.engine import _encode_state
+    for L in (4, 10, 32):
+        eng = TDEngine(L, 2, "def", False, 1, np_seeds=[1, 2], py_seeds=[1, 2], autoreset=False)
+        try:
+            assert eng.state_bytes(2) == _encode_state(eng.export_state(), 2, L).nbytes, L
+        finally:
+            eng.close()
 
 
 def test_step_kernel_selector():
