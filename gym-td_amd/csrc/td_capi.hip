@@ -21,6 +21,7 @@
 
 #include "../../include/tdstep.h"
 #include "../../include/td_diag.h"
+#include "../../include/td_diag_retained.h"
 #include "td_copy_check.h"
 #include "td_ids_check.h"
 #include "td_kernel_choice.h"
@@ -90,7 +91,13 @@ struct td_handle {
   int L = 0, NC = 0, B = 0, mode = 0, multi = 0, difficulty = 1, device = 0, autoreset = 1;
   int opp_np = 0;  // random_agent=False
   int small = 0, obs_wt = 0;  // the step kernel (0 large, 1 small, 2 small2), write-through observation stores
-  int kernel_forced = 0;      // td_set_step_kernel chose the kind (else TD_KERNEL_AUTO: auto_kernel)
+  int kernel_forced = 0;      // td_set_step_kernel chose the kind (else TD_KERNEL_AUTO: auto_kernel_kind)
+  // A skipping launch (a td_step into the retained buffer with StepArgs::obs_skip) runs a kind
+  // of its own (td_kernel_choice.h retained_kernel_kind): `small` stays the kind of a launch
+  // that writes every window.
+  int small_retained = 0, obs_wt_retained = 0;
+  int retained_forced = 0;    // td_set_step_kernel or td_set_retained_step_kernel chose small_retained
+  int name_kind = 0;          // the kind td_step_kernel_name names: of the last td_step's launch, else `small`
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
@@ -307,22 +314,22 @@ void parallel_for(int n, F fn) {
   for (auto& t : pool) t.join();
 }
 
-// The step kernel (td_set_step_kernel): small = 0 large, 1 small, 2 small2, and whether its
-// observation stores are write-through (td_kernel_choice.h obs_write_through).
-int apply_kernel(td_handle* h, int small) {
-  h->small = small;
-  h->obs_wt = obs_write_through(small, h->L, h->obs_fmt, h->B);
-  // (while frame skip is on, td_step launches the skip kernel whatever kind is kept here)
-  // (for an aligned observation buffer: launch_step takes the large kernel for any other)
-  const StepArgs a = base_args(h);
-  h->kernel_name = kernel_display_name(h->frame_skip > 1 ? skip_row(a) : step_row(a, a.small));
-  return 0;
-}
-
-// TD_KERNEL_AUTO (td_kernel_choice.h auto_kernel_kind); td_set_step_kernel overrides.
-int auto_kernel(const td_handle* h) {
+// Both step kernels of the handle (0 large, 1 small, 2 small2), resolved from what was forced
+// (kernel_forced / retained_forced: h->small / h->small_retained as they stand) and the rules
+// of td_kernel_choice.h, and whether each kind's observation stores are write-through.  The
+// name goes back to the kernel of a launch that writes every window.
+int apply_kernel(td_handle* h) {
   const int* r = h->resident[h->obs_fmt == TD_OBS_F16];
-  return auto_kernel_kind(h->L, h->mode, h->multi, h->obs_fmt, h->B, r[0], r[1]);
+  const StepKinds k = resolve_step_kinds(h->kernel_forced ? h->small : -1, h->retained_forced ? h->small_retained : -1,
+                                         h->L, h->mode, h->multi, h->obs_fmt, h->B, r[0], r[1]);
+  h->small = k.full;
+  h->small_retained = k.retained;
+  h->obs_wt = obs_write_through(k.full, h->L, h->obs_fmt, h->B);
+  h->obs_wt_retained = obs_write_through(k.retained, h->L, h->obs_fmt, h->B);
+  // (while frame skip is on, td_step launches the skip kernel whatever kinds are kept here)
+  // (for an aligned observation buffer: launch_step takes the large kernel for any other)
+  h->name_kind = k.full;
+  return 0;
 }
 
 // Drop staged layouts: they were drawn from a stream that has been replaced.
@@ -598,7 +605,7 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
       h->resident[f][0] = step_resident_boards(ra, cus, 1);
       h->resident[f][1] = step_resident_boards(ra, cus, 2);
     }
-    if (apply_kernel(h, auto_kernel(h))) return create_failed(h);
+    if (apply_kernel(h)) return create_failed(h);
   }
   std::vector<uint32_t> seeds(B);
   for (size_t b = 0; b < B; ++b) seeds[b] = (uint32_t)b;
@@ -938,7 +945,17 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   const EvPair ev = (h->steps - h->tev_from) % h->tev_every == 0 ? next_timing_pair(h) : EvPair{};
   // frame skip: one launch of the skip kernel runs the k board steps (td_step_skip.h).  The refill
   // cadence and the ring guard above count launches: a board consumes at most one layout per launch.
-  HIP_OK(h->frame_skip > 1 ? launch_skip(a, s, ev.e0, ev.e1) : launch_step(a, s, ev.e0, ev.e1));
+  if (h->frame_skip > 1) {
+    HIP_OK(launch_skip(a, s, ev.e0, ev.e1));
+  } else {
+    // the kernel is chosen per launch: a launch that writes every window is bound by its stores,
+    // a skipping launch by the boards in flight (td_kernel_choice.h retained_kernel_kind)
+    const int kind = a.obs_skip ? h->small_retained : h->small;
+    a.small = kind;
+    a.obs_wt = a.obs_skip ? h->obs_wt_retained : h->obs_wt;
+    HIP_OK(launch_step(a, kind, s, ev.e0, ev.e1));
+    h->name_kind = step_launch_kind(a, kind);
+  }
   if (h->autoreset && h->opp_np) HIP_OK(launch_autoreset(a, s));
   h->steps += 1;
   h->since_guard += 1;
@@ -1031,22 +1048,40 @@ int td_set_step_kernel(td_handle* h, int kind) {
   if (kind >= TD_KERNEL_SMALL && h->L != 10 && h->L != 20 && h->L != 30)
     return fail("td_set_step_kernel: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", h->L);
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
-  h->kernel_forced = kind != TD_KERNEL_AUTO;
-  return apply_kernel(h, kind == TD_KERNEL_AUTO ? auto_kernel(h) : kind - 1);
+  // a forced kind is forced for every launch, skipping or not; TD_KERNEL_AUTO gives both back to their rules
+  h->kernel_forced = h->retained_forced = kind != TD_KERNEL_AUTO;
+  if (kind != TD_KERNEL_AUTO) h->small = h->small_retained = kind - 1;
+  return apply_kernel(h);
+}
+
+// Skipping launches only: TD_KERNEL_AUTO gives their kind back to the rule (on the full kind as
+// it stands, forced or not), any other kind forces it.  The kind of a launch that writes every
+// window stays.
+int td_set_retained_step_kernel(td_handle* h, int kind) {
+  if (!h) return fail("NULL handle");
+  if (kind < TD_KERNEL_AUTO || kind > TD_KERNEL_SMALL2) return fail("td_set_retained_step_kernel: unknown kernel kind %d", kind);
+  if (kind >= TD_KERNEL_SMALL && h->L != 10 && h->L != 20 && h->L != 30)
+    return fail("td_set_retained_step_kernel: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", h->L);
+  HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
+  h->retained_forced = kind != TD_KERNEL_AUTO;
+  if (kind != TD_KERNEL_AUTO) h->small_retained = kind - 1;
+  return apply_kernel(h);
 }
 
 int td_step_kernel(td_handle* h) { return h ? h->small + 1 : fail("NULL handle"); }
 
+int td_retained_step_kernel(td_handle* h) { return h ? h->small_retained + 1 : fail("NULL handle"); }
+
 // The observation's element.  A kernel kind the caller forced stays, TD_KERNEL_AUTO is
-// resolved again for the new format (auto_kernel); the write-through policy and the
-// kernel's name follow the new byte size.
+// resolved again for the new format (apply_kernel), for both kinds of launch; the write-through
+// policy and the kernel's name follow the new byte size.
 int td_set_obs_format(td_handle* h, int fmt) {
   if (!h) return fail("NULL handle");
   if (fmt != TD_OBS_F32 && fmt != TD_OBS_F16) return fail("td_set_obs_format: unknown format %d (TD_OBS_F32 = 0, TD_OBS_F16 = 1)", fmt);
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep the format they were enqueued with
   h->obs_fmt = fmt;
   h->ledger.touch();  // (the same format again too: the caller may have changed the buffer's element)
-  return apply_kernel(h, h->kernel_forced ? h->small : auto_kernel(h));
+  return apply_kernel(h);
 }
 
 int td_obs_format(td_handle* h) { return h ? h->obs_fmt : fail("NULL handle"); }
@@ -1061,7 +1096,7 @@ int td_set_frame_skip(td_handle* h, int k) {
   if (k > 1 && h->opp_np) return fail("td_set_frame_skip: k = %d > 1 is not supported with random_agent=False", k);
   HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
   h->frame_skip = k;
-  return apply_kernel(h, h->small);
+  return apply_kernel(h);
 }
 
 int td_frame_skip(td_handle* h) { return h ? h->frame_skip : fail("NULL handle"); }
@@ -1080,7 +1115,14 @@ int td_retain_obs(td_handle* h, const void* obs) {
 
 const void* td_retained_obs(td_handle* h) { return h ? h->ledger.retained : nullptr; }
 
-const char* td_step_kernel_name(td_handle* h) { return h ? h->kernel_name.c_str() : ""; }
+// The kernel of the most recent td_step; before it, and after a kernel, format or frame-skip
+// change, the kernel of a launch that writes every window (apply_kernel).
+const char* td_step_kernel_name(td_handle* h) {
+  if (!h) return "";
+  const StepArgs a = base_args(h);
+  h->kernel_name = kernel_display_name(h->frame_skip > 1 ? skip_row(a) : step_row(a, h->name_kind));
+  return h->kernel_name.c_str();
+}
 
 int td_set_refill_interval(td_handle* h, int steps) {
   if (!h || steps < 0) return fail("td_set_refill_interval: bad arguments");

@@ -44,6 +44,60 @@ inline int auto_kernel_kind(int L, int mode, int multi, int obs_fmt, int B, int 
                                                       : 0;
 }
 
+// The kind of a skipping launch under TD_KERNEL_AUTO: a td_step into the retained buffer that
+// leaves clean windows unwritten (StepArgs::obs_skip, td_obs_ledger.h).  full_kind is the kind
+// of a launch that writes every window (auto_kernel_kind, or what td_set_step_kernel forced):
+// that launch is bound by its stores, a skipping launch writes ~7.7 of 18.3 KB per board at
+// 10x10 and is bound by the boards in flight -- so the second wave of small2, which halves
+// them, has almost nothing left to write.  Returns full_kind wherever the sweep
+// (scripts/retained_kernel_bench.py, three alternating 200-step blocks per kernel) shows no
+// gain whose slowest block is below full_kind's fastest.  Every row was measured against
+// both other kernels, so it holds whatever full_kind is.
+// us per step, fastest-slowest of three blocks, profiles/retained_kernel/sweep.jsonl:
+//   float32 L = 10 above one round of boards: the one-wave small kernel in every mode --
+//     TD-def     12,288   small 41.8-42.3    small2 43.6-44.4    large 43.0-44.1
+//                16,384         51.6-52.0           55.0-55.9          54.4-65.6
+//                32,768         92.4-93.9           101.8-103.4        99.3-169.6
+//                65,536         173.5-175.7         193.9-197.6        187.3-229.2
+//     TD-atk     16,384         78.5-82.6           87.1-91.2          83.3-88.1
+//                65,536         229.1-250.1         293.7-313.7        265.4-286.7
+//     TD-2p      16,384         52.0-53.0           55.9-57.6          55.0-69.7
+//                65,536         168.8-170.5         196.7-199.6        183.2-185.1
+//     TD-def multi-action 16,384  61.0-61.6         64.3-64.8          67.1-81.6
+//                65,536         191.0-193.0         217.7-218.9        221.1-221.6
+//     TD-2p multi-action 16,384   61.7-62.2         65.4-66.1          66.8-71.6
+//   L = 20 TD-2p multi-action 16,384: small2 189.2-191.0 vs 197.4-200.0 small, 197.5-200.3 large;
+//   L = 30 TD-def 16,384: small2 278.0-281.1 vs 291.8-294.3 small, 292.9-294.9 large -- the full
+//   kind stays: on the larger maps the second wave still pays.
+//   The bench line (65,536 TD-def boards, burn-in 1,200): 439.0-440.3 vs 388.2-391.9 M env-steps/s,
+//   148.9-149.3 vs 167.2-168.8 us per step, three alternating runs (bench_branch_*, bench_parent_*).
+//   Up to one round of boards every board is in flight with any kernel: the full kind stays.
+//   float16 at L = 10 runs the small kernel above half a round already (auto_kernel_kind).
+inline int retained_kernel_kind(int L, int mode, int multi, int obs_fmt, int B, int resident, int resident2,
+                                int full_kind) {
+  (void)mode; (void)multi; (void)resident2;
+  if (resident <= 0 || B <= resident) return full_kind;
+  if (obs_fmt == TD_OBS_F32 && L == 10) return 1;
+  return full_kind;
+}
+
+// Both kinds of a handle.  forced_full / forced_retained: a kind the caller forced (0 .. 2),
+// or -1 for TD_KERNEL_AUTO.  td_set_step_kernel forces both (a forced kind is forced for every
+// launch), td_set_retained_step_kernel the second only; an unforced retained kind follows the
+// rule on the full kind as resolved, forced or not.
+struct StepKinds {
+  int full, retained;
+};
+inline StepKinds resolve_step_kinds(int forced_full, int forced_retained, int L, int mode, int multi, int obs_fmt, int B,
+                                    int resident, int resident2) {
+  StepKinds k;
+  k.full = forced_full >= 0 ? forced_full : auto_kernel_kind(L, mode, multi, obs_fmt, B, resident, resident2);
+  k.retained = forced_retained >= 0
+                   ? forced_retained
+                   : retained_kernel_kind(L, mode, multi, obs_fmt, B, resident, resident2, k.full);
+  return k;
+}
+
 // Write-through observation stores go with the small kernels where the batch's observation
 // fits the 256-MiB Infinity Cache (scripts/storepol.hip: 21.8 vs 30.0 us at 8,192 boards).
 // (Write-through beyond the Infinity Cache -- any kernel, TD_OBS_WT=1 -- measured 1.5-1.7x

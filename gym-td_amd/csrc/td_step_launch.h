@@ -92,13 +92,20 @@ inline hipError_t launch_row(const KernelRow& k, int grid, void** args, hipStrea
 // The observation's store unit per format (td_step_obs.h ObsFmt<OT>::UB; the step units assert it).
 constexpr int kObsUnitF32 = 16, kObsUnitF16 = 8;
 
-// The step of a.small's kernel, or of the large kernel (its per-element path) where the
-// observation is not aligned to the format's store unit.
-inline hipError_t launch_step(const StepArgs& a, hipStream_t s, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+// The kind a step into a.obs launches where `kind` is asked for: the large kernel (its
+// per-element path) where the observation is not aligned to the format's store unit.
+inline int step_launch_kind(const StepArgs& a, int kind) {
   const uintptr_t unit = a.obs_f16 ? kObsUnitF16 : kObsUnitF32;
   const bool aligned = (reinterpret_cast<uintptr_t>(a.obs) & (unit - 1)) == 0;
+  return aligned ? kind : 0;
+}
+
+// The step of this launch's kind (the caller's choice between the handle's two kinds: a launch
+// that writes every window, a skipping launch), or of the large kernel for an unaligned buffer.
+inline hipError_t launch_step(const StepArgs& a, int kind, hipStream_t s, hipEvent_t ev0 = nullptr,
+                              hipEvent_t ev1 = nullptr) {
   void* args[] = {const_cast<StepArgs*>(&a)};
-  return launch_row(step_row(a, aligned ? a.small : 0), a.B, args, s, ev0, ev1);
+  return launch_row(step_row(a, step_launch_kind(a, kind)), a.B, args, s, ev0, ev1);
 }
 
 // Frame skip (a.frame_skip > 1): a.frame_skip board steps per board in one launch of the skip

@@ -118,6 +118,7 @@ def _load():
         "td_set_frame_skip": (ctypes.c_int, [c_vp, ctypes.c_int]),
         "td_frame_skip": (ctypes.c_int, [c_vp]),
         "td_step_kernel": (ctypes.c_int, [c_vp]),
+        "td_retained_step_kernel": (ctypes.c_int, [c_vp]),
         "td_step_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_step_boards_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_config_epoch": (ctypes.c_int, [c_vp]),
@@ -126,6 +127,7 @@ def _load():
         "td_guard_timeouts": (ctypes.c_int, [c_vp, ctypes.c_int]),
         # test / measurement hooks (include/td_diag.h): not the drop-in surface
         "td_set_step_kernel": (ctypes.c_int, [c_vp, ctypes.c_int]),
+        "td_set_retained_step_kernel": (ctypes.c_int, [c_vp, ctypes.c_int]),  # include/td_diag_retained.h
         "td_board_map": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, c_i32p]),
         "td_set_store_policy": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
         "td_debug_set_claim": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),

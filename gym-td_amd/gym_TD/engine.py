@@ -146,7 +146,10 @@ class TDEngine(object):
           each board's layout stream; with auto-reset the next layout is then drawn
           right after the step that ends the episode, in stream order).
     step_kernel: 'auto' (td_create's rule by batch size), 'large', 'small' or 'small2'
-          (td_set_step_kernel; the three give the same results).
+          (td_set_step_kernel; the three give the same results).  'auto' chooses per
+          launch: a step that skips clean windows of the retained observation may run
+          another kernel than one that writes every window (retained_step_kernel); a
+          forced kind runs for every launch.
     obs_dtype: torch.float32 (default) or torch.float16: the element of ``obs``.  The
           float16 observation is the float32 one rounded to nearest-even, written by the
           step kernels themselves (td_set_obs_format): half the step's store stream and
@@ -558,6 +561,14 @@ class TDEngine(object):
             raise ValueError("step kernel must be one of %s" % sorted(_lib.STEP_KERNELS))
         _lib.check(_lib.lib.td_set_step_kernel(self._h, _lib.STEP_KERNELS[kind]))
 
+    def set_retained_step_kernel(self, kind):
+        """The step kernel of skipping launches only -- steps into the retained observation that
+        leave clean windows unwritten: 'auto' (the rule), 'large', 'small' or 'small2'
+        (td_set_retained_step_kernel, a measurement hook).  set_step_kernel overrides it."""
+        if kind not in _lib.STEP_KERNELS:
+            raise ValueError("step kernel must be one of %s" % sorted(_lib.STEP_KERNELS))
+        _lib.check(_lib.lib.td_set_retained_step_kernel(self._h, _lib.STEP_KERNELS[kind]))
+
     def set_frame_skip(self, k):
         """Board steps per step() from the next step on (td_set_frame_skip): 1 .. 16.  No
         board state changes; refused (TDError) with k > 1 on a multi-action or
@@ -588,13 +599,21 @@ class TDEngine(object):
 
     @property
     def step_kernel(self):
-        """The step kernel td_step launches: 'large', 'small' or 'small2'."""
+        """The step kernel of a td_step that writes every window: 'large', 'small' or 'small2'."""
         k = _lib.check(_lib.lib.td_step_kernel(self._h))
         return {v: n for n, v in _lib.STEP_KERNELS.items()}[k]
 
     @property
+    def retained_step_kernel(self):
+        """The step kernel of a skipping launch (a step into the retained observation):
+        'large', 'small' or 'small2' (td_retained_step_kernel)."""
+        k = _lib.check(_lib.lib.td_retained_step_kernel(self._h))
+        return {v: n for n, v in _lib.STEP_KERNELS.items()}[k]
+
+    @property
     def step_kernel_name(self):
-        """Its name as rocprofv3 reports it, e.g. 'td_step_kernel_small<10, 0, false>'."""
+        """The kernel of the most recent step (before the first: of a step that writes every
+        window) as rocprofv3 reports it, e.g. 'td_step_kernel_small<10, 0, false>'."""
         return _lib.lib.td_step_kernel_name(self._h).decode()
 
     def set_store_policy(self, xcd_map=1, edge_wt=2):

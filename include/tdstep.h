@@ -440,13 +440,28 @@ int td_action_mask(td_handle* h, const td_mask_io* io, void* stream);
  *                    L = 30 (single-action) and 8 rounds for TD-2p multi-action at L = 20 --
  *                    else LARGE (L = 10 / 20 / 30; other L only have LARGE).  With
  *                    TD_OBS_F16 at L = 10: SMALL2 up to half a round, SMALL above.
+ * The kernel is chosen per launch.  The rule above is the kind of a launch that writes every
+ * window of the observation: every td_step of a handle that retains nothing, and with
+ * td_retain_obs the first step and any step after the buffer stopped being known (the list
+ * above td_retain_obs).  Such a launch is bound by its stores.  A skipping launch -- a td_step
+ * into the retained buffer that leaves clean windows unwritten -- stores less than half the
+ * bytes and is bound by the boards in flight, so TD_KERNEL_AUTO resolves a second kind for it:
+ * the first kind, except where a kernel with more boards in flight measured faster --
+ * float32, L = 10, single-action TD-def above one round of boards: SMALL where the first kind
+ * is SMALL2 (DESIGN.md section 4 has the measurements).  Both kinds see the same board state
+ * and give the same results, so the hand-over between them needs nothing.
  * The small kernels need a 16-B-aligned observation buffer (8-B-aligned with TD_OBS_F16);
- * a td_step with any other buffer runs LARGE.  (Forcing a kind is a test hook: td_set_step_kernel, td_diag.h.)
- * td_step_kernel returns the resolved kind, td_step_kernel_name the
+ * a td_step with any other buffer runs LARGE.  (Forcing a kind is a test hook: td_set_step_kernel, td_diag.h;
+ * a kind forced there is forced for every launch.)
+ * td_step_kernel returns the resolved kind of a launch that writes every window,
+ * td_retained_step_kernel that of a skipping launch.  td_step_kernel_name is the
  * kernel's name as rocprofv3 shows it ("td_step_kernel_small<10, 0, false>": L, mode,
- * multi-action scan). */
+ * multi-action scan): the kernel the most recent td_step launched; before the first td_step,
+ * and after a change of kernel, format or frame skip, the kernel of a launch that writes every
+ * window.  The string is the handle's, valid until the next call. */
 enum td_step_kernel_kind { TD_KERNEL_AUTO = 0, TD_KERNEL_LARGE = 1, TD_KERNEL_SMALL = 2, TD_KERNEL_SMALL2 = 3 };
 int td_step_kernel(td_handle* h);
+int td_retained_step_kernel(td_handle* h);
 const char* td_step_kernel_name(td_handle* h);
 /* The kernel td_step_boards launches on this handle, as rocprofv3 shows it:
  * "td_step_sel_kernel<10, 0, false>" (L or 0 for a generic side, mode, multi-action scan), or
