@@ -22,6 +22,7 @@
 #include "../../include/tdstep.h"
 #include "../../include/td_diag.h"
 #include "../../include/td_diag_retained.h"
+#include "td_cfg_check.h"
 #include "td_copy_check.h"
 #include "td_ids_check.h"
 #include "td_kernel_choice.h"
@@ -188,6 +189,7 @@ void build_dev_cfg(const td_config& c, TdDevCfg& d) {
   d.enemy_upgrade_at = c.enemy_upgrade_at;
   d.def_init_cost = c.defender_init_cost;
   d.atk_init_cost = c.attacker_init_cost;
+  // integers within int32 by check_cfg (td_cfg_check.h): the conversions are exact
   d.frozen_time = (int32_t)c.frozen_time;
   d.base_LP = (int32_t)c.base_LP;
   d.tower_distance = (int32_t)c.tower_distance;
@@ -198,18 +200,10 @@ void build_dev_cfg(const td_config& c, TdDevCfg& d) {
   d.max_tower_lv = c.max_tower_lv;
 }
 
+// The checks themselves: td_cfg_check.h (run alone by scripts/cfg_check_host.cpp).
 int check_cfg(const td_config& c) {
-  if (c.enemy_types != 4 || c.tower_types != 4) return fail("enemy_types / tower_types must be 4 (obs has 45 channels)");
-  if (c.max_enemy_lv != 1 || c.max_tower_lv < 0 || c.max_tower_lv > 1) return fail("max_enemy_lv must be 1, max_tower_lv 0 or 1");
-  if (c.max_cluster_length != 8 || c.max_num_of_roads != 3) return fail("max_cluster_length must be 8, max_num_of_roads 3");
-  if (c.max_episode_steps <= 0) return fail("max_episode_steps must be > 0");
-  if (c.tower_distance < 0 || c.tower_distance > 15) return fail("tower_distance out of range");
-  if (c.frozen_time < 0 || c.frozen_time > 255) return fail("frozen_time must be in [0, 255] (8-bit slowdown)");
-  if (c.base_LP < 1) return fail("base_LP must be a positive int (None is not supported)");
-  for (int t = 0; t < 4; ++t)
-    for (int l = 0; l < 2; ++l)
-      if (c.enemy_LP[t][l] <= 0) return fail("enemy_LP must be > 0");
-  return 0;
+  char msg[200] = "";
+  return cfg_check(c, msg, sizeof msg) == CFG_OK ? 0 : fail("%s", msg);
 }
 
 // Device allocations.  The library's own arrays are plain hipMalloc: every state array
@@ -650,6 +644,20 @@ int td_set_config(td_handle* h, const td_config* cfg) {
   build_dev_cfg(*cfg, d);
   HIP_OK(hipDeviceSynchronize());
   if (std::memcmp(&d, &h->dcfg, sizeof d) == 0) return 0;  // nothing changed
+  // tower_distance may not grow while a board holds a tower.  The reference subtracts a destructed
+  // tower's diamond at the CURRENT tower_distance (TDBoard.py:281-287): wider than the one it added,
+  // it takes map[6] below zero on cells it never counted, and to zero under another tower -- a free
+  // cell, so a second tower can stand on a cell that has one.  A cell word has an unsigned count and
+  // room for one tower: neither state can be represented, so the change that leads there is refused.
+  if (d.tower_distance > h->dcfg.tower_distance) {
+    std::vector<TdHdr> hdr((size_t)h->B);
+    HIP_OK(hipMemcpy(hdr.data(), h->d_hdr, hdr.size() * sizeof(TdHdr), hipMemcpyDeviceToHost));
+    for (int b = 0; b < h->B; ++b)
+      if (hdr[(size_t)b].n_tw > 0)
+        return fail("td_set_config: tower_distance may not grow (%d -> %d) while a board holds a tower (board %d has %d): "
+                    "reset the boards, or destruct the towers, first",
+                    h->dcfg.tower_distance, d.tower_distance, b, hdr[(size_t)b].n_tw);
+  }
   int slot = -1;
   if (h->cfg_fresh < NCFG) {
     slot = h->cfg_fresh++;

@@ -49,12 +49,31 @@ _live = weakref.WeakSet()
 
 
 def paramConfig(**kwargs):
-    """TDParam.py:98-100; also re-uploads the constant block of live engines."""
+    """TDParam.py:98-100; also re-uploads the constant block of live engines.
+
+    A config the device cannot represent -- a fractional frozen_time, base_LP, tower_distance
+    or action interval (the device keeps them as integers), a negative interval, a NaN or an
+    infinity anywhere, a tower_distance that grows while a board holds a tower
+    (include/tdstep.h, td_config) -- raises TDError, as the engines' other
+    setters do, and ``config`` keeps the values it had.  It is the live engines that check:
+    with none, such a value is stored as it is and the next ``TDEngine(...)`` raises.  With
+    several, they are updated in turn; if one raises for a reason of its own (256 config epochs
+    still referenced), those before it already run the new config while ``config`` is restored."""
+    missing = object()
+    old = {key: getattr(config, key, missing) for key in kwargs}
     for key, val in kwargs.items():
         setattr(config, key, val)
-    for eng in list(_live):
-        if getattr(eng, "_h", None):  # closed engines are gone
-            eng.set_config(config)
+    try:
+        for eng in list(_live):
+            if getattr(eng, "_h", None):  # closed engines are gone
+                eng.set_config(config)
+    except _lib.TDError:
+        for key, val in old.items():
+            if val is missing:
+                delattr(config, key)
+            else:
+                setattr(config, key, val)
+        raise
 
 
 def getConfig():

@@ -397,7 +397,9 @@ static void get_states(const Env* e, float* s) {
     }
   S(4, e->end[0], e->end[1]) = 1.0f;
   for (int i = 0; i < e->num_roads; ++i) S(6 + i, e->start[i][0], e->start[i][1]) = 1.0f;
-  const int lv0 = 15, ty0 = lv0 + (int)c->max_tower_lv + 1;
+  /* 45 planes whatever max_tower_lv is, as on the device: with max_tower_lv = 0 the reference's
+   * observation has 44 (TDBoard.py:129,154), and plane 16 here stays zero. */
+  const int lv0 = 15, ty0 = 17;
   for (int i = 0; i < e->n_tw; ++i) {
     const Tower* w = &e->tw[i];
     S(lv0 + w->lv, w->r, w->c) = 1.0f;

@@ -1,6 +1,12 @@
 """Generate golden vectors from the upstream reference (run in the build container only).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_golden.py [--only NAME...]
+
+``--only`` writes the named fixtures alone (a trajectory's name, ``kat`` or ``roadgen``), so
+that adding one rewrites no other.  The ``cfg_*`` trajectories run under fuzzed configs:
+their overrides are ``tests/cfgspace.py``'s ``draw(seed, regime)``, every double with a full
+mantissa.  Every recorded observation has 45 planes: under max_tower_lv = 0 (``cfg_def10_lv0``)
+the reference's 44 with an all-zero plane 16 put in (``cfgspace.pad_obs``), as the device writes it.
 
 Writes small fixtures next to this file.  Each fixture records, for a seeded
 run of the REFERENCE env (loaded read-only by ``refloader``), the inputs
@@ -26,8 +32,10 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 
+import cfgspace  # noqa: E402
 import refloader  # noqa: E402
 from oracle import canon, policies  # noqa: E402
 
@@ -127,7 +135,7 @@ def run(name, mode, L, seed, steps, difficulty=1, multi=False, smart=0.0, overri
         b.step = rec
 
     hook()
-    first = env._board.get_states()
+    first = cfgspace.pad_obs(env._board.get_states())
     out = {"name": name, "mode": mode, "L": L, "seed": seed, "opp_seed": opp_seed, "difficulty": difficulty,
            "multi": multi, "smart": smart, "overrides": overrides, "policy_seed": seed + 1000003,
            "init": {"o": canon.obs_digest(first), "lay": layout_of(env), "nr": int(env.num_roads),
@@ -157,6 +165,7 @@ def run(name, mode, L, seed, steps, difficulty=1, multi=False, smart=0.0, overri
             obs = env._board.get_states()
             done = env._board.done()
             rew = box[0] if mode != "atk" else -box[0]
+        obs = cfgspace.pad_obs(obs)  # 45 planes whatever max_tower_lv is (44 in the reference at 0)
         rstate = random.getstate()
         rec = {"r": canon.fhex(rew), "d": int(bool(done)), "o": canon.obs_digest(obs),
                "s": canon.state_digest(ref_state(env))}
@@ -176,7 +185,7 @@ def run(name, mode, L, seed, steps, difficulty=1, multi=False, smart=0.0, overri
         if done:
             signal.alarm(5)
             try:
-                o2 = env.reset()
+                o2 = cfgspace.pad_obs(env.reset())
                 signal.alarm(0)
             except Timeout:
                 out["records"].append({"reset_error": "hang"})
@@ -230,8 +239,7 @@ def kat():
     print("kat: summons", summons)
 
 
-def main():
-    kat()
+def roadgen():
     table = {}
     for L in (10, 20, 30):
         table[str(L)] = roadgen_table(L, range(0, 400))
@@ -239,27 +247,69 @@ def main():
         print("roadgen L=%d errors=%d" % (L, errs))
     with gzip.open(os.path.join(HERE, "roadgen.json.gz"), "wt") as f:
         json.dump(table, f, separators=(",", ":"))
-    run("def10_s21", "def", 10, 21, 1500, smart=0.6)
-    run("def10_s2", "def", 10, 2, 1500, smart=0.0)
-    run("def10_s3", "def", 10, 3, 1500, smart=0.9)
-    run("def10_lv0_s4", "def", 10, 4, 1000, difficulty=0, smart=0.6)
-    run("def20_s5", "def", 20, 5, 1300, smart=0.7)
-    run("def20_s6", "def", 20, 6, 800, smart=0.0)
-    run("def30_s7", "def", 30, 7, 1300, smart=0.7)
-    run("def30_s8", "def", 30, 8, 600, smart=0.2)
-    run("def10_cfg_s9", "def", 10, 9, 1300, smart=0.9,
-        overrides={"enemy_upgrade_at": 0.05, "base_LP": 40, "defender_init_cost": 60, "max_cost": 150,
-                   "frozen_time": 3, "tower_distance": 1, "defender_cost_rate": 0.35,
-                   "tower_splash_range": [[0, 1], [0, 0], [1, 2], [1, 1]]})
-    run("defmulti10_s11", "def", 10, 11, 400, multi=True)
-    run("2pmulti20_s12", "2p", 20, 12, 300, multi=True)
-    run("2pmulti20_s13", "2p", 20, 13, 300, multi=True)
-    run("2p20_s14", "2p", 20, 14, 600, smart=0.6)
-    run("atk10_lv0_s15", "atk", 10, 15, 500, difficulty=0)
-    run("atk10_lv1_s16", "atk", 10, 16, 500, difficulty=1)
-    run("atk10_lv2_s17", "atk", 10, 17, 500, difficulty=2)
+
+
+def fuzzed(seed, regime, max_tower_lv=1):
+    ov = cfgspace.draw(seed, regime)
+    assert ov["max_tower_lv"] == max_tower_lv, (seed, regime)
+    return ov
+
+
+# (name, mode, L, seed, steps, keyword arguments of run)
+RUNS = [
+    ("def10_s21", "def", 10, 21, 1500, dict(smart=0.6)),
+    ("def10_s2", "def", 10, 2, 1500, dict(smart=0.0)),
+    ("def10_s3", "def", 10, 3, 1500, dict(smart=0.9)),
+    ("def10_lv0_s4", "def", 10, 4, 1000, dict(difficulty=0, smart=0.6)),
+    ("def20_s5", "def", 20, 5, 1300, dict(smart=0.7)),
+    ("def20_s6", "def", 20, 6, 800, dict(smart=0.0)),
+    ("def30_s7", "def", 30, 7, 1300, dict(smart=0.7)),
+    ("def30_s8", "def", 30, 8, 600, dict(smart=0.2)),
+    ("def10_cfg_s9", "def", 10, 9, 1300, dict(smart=0.9, overrides={
+        "enemy_upgrade_at": 0.05, "base_LP": 40, "defender_init_cost": 60, "max_cost": 150,
+        "frozen_time": 3, "tower_distance": 1, "defender_cost_rate": 0.35,
+        "tower_splash_range": [[0, 1], [0, 0], [1, 2], [1, 1]]})),
+    ("defmulti10_s11", "def", 10, 11, 400, dict(multi=True)),
+    ("2pmulti20_s12", "2p", 20, 12, 300, dict(multi=True)),
+    ("2pmulti20_s13", "2p", 20, 13, 300, dict(multi=True)),
+    ("2p20_s14", "2p", 20, 14, 600, dict(smart=0.6)),
+    ("atk10_lv0_s15", "atk", 10, 15, 500, dict(difficulty=0)),
+    ("atk10_lv1_s16", "atk", 10, 16, 500, dict(difficulty=1)),
+    ("atk10_lv2_s17", "atk", 10, 17, 500, dict(difficulty=2)),
+    # fuzzed configs (tests/cfgspace.py): one per regime in TD-def, TD-atk, TD-2p discrete and
+    # multi-action, and a 30x30 map
+    ("cfg_def10_bal", "def", 10, 31, 400, dict(smart=0.8, overrides=lambda: fuzzed(CFG_SEEDS[0], "balanced"))),
+    ("cfg_def10_swarm", "def", 10, 32, 400, dict(difficulty=0, smart=0.8, overrides=lambda: fuzzed(CFG_SEEDS[1], "swarm"))),
+    ("cfg_def10_fort", "def", 10, 33, 400, dict(smart=0.8, overrides=lambda: fuzzed(CFG_SEEDS[2], "fortress"))),
+    ("cfg_def10_sprint", "def", 10, 34, 400, dict(difficulty=0, smart=0.8, overrides=lambda: fuzzed(CFG_SEEDS[3], "sprint"))),
+    ("cfg_atk10_lv2", "atk", 10, 35, 400, dict(difficulty=2, overrides=lambda: fuzzed(CFG_SEEDS[4], "balanced"))),
+    ("cfg_2p10", "2p", 10, 36, 400, dict(smart=0.8, overrides=lambda: fuzzed(CFG_SEEDS[5], "swarm"))),
+    ("cfg_2pmulti20", "2p", 20, 37, 300, dict(multi=True, overrides=lambda: fuzzed(CFG_SEEDS[6], "fortress"))),
+    ("cfg_def30", "def", 30, 38, 300, dict(smart=0.8, overrides=lambda: fuzzed(CFG_SEEDS[7], "balanced"))),
+    # max_tower_lv = 0: the reference's observation has 44 planes, recorded with plane 16 put in
+    ("cfg_def10_lv0", "def", 10, 39, 400, dict(smart=0.8, overrides=lambda: fuzzed(71, "fortress", max_tower_lv=0))),
+]
+CFG_SEEDS = (54, 65, 53, 64, 54, 46, 48, 66)  # cfgspace.draw seeds of the eight cfg_* runs, in RUNS' order
+
+
+def main(argv):
+    only = None
+    if argv and argv[0] == "--only":
+        only = set(argv[1:])
+        known = {"kat", "roadgen"} | {r[0] for r in RUNS}
+        assert only and only <= known, sorted(only - known)
+    if only is None or "kat" in only:
+        kat()
+    if only is None or "roadgen" in only:
+        roadgen()
+    for name, mode, L, seed, steps, kw in RUNS:
+        if only is None or name in only:
+            kw = dict(kw)
+            if callable(kw.get("overrides")):
+                kw["overrides"] = kw["overrides"]()
+            run(name, mode, L, seed, steps, **kw)
     set_config({}, False)
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

@@ -8,6 +8,7 @@ import zlib
 
 import numpy as np
 
+from cfgspace import pad_obs
 from oracle import canon, policies
 from oracle import td_oracle as O
 
@@ -76,7 +77,8 @@ def replay_oracle(tr, max_steps=None):
     """Replay a golden trajectory with the oracle; yields (index, record, produced) tuples."""
     env = oracle_env(tr)
     nxt = action_stream(tr, lambda: env._board.map[0])
-    first = env._board.get_states()
+    # (pad_obs: the fixtures' observations have 45 planes whatever max_tower_lv is, as the device's)
+    first = pad_obs(env._board.get_states())
     yield -1, tr["init"], {"o": canon.obs_digest(first), "lay": canon.layout_digest(env._board.map, env._board.start, env._board.end),
                            "nr": int(env.num_roads), "s": canon.state_digest(canon.oracle_state(env))}
     k = 0
@@ -90,7 +92,7 @@ def replay_oracle(tr, max_steps=None):
             yield i, rec, {"reset_error": got}
             return
         if "reset" in rec:
-            o = env.reset()
+            o = pad_obs(env.reset())
             yield i, rec, {"reset": 1, "o": canon.obs_digest(o),
                            "lay": canon.layout_digest(env._board.map, env._board.start, env._board.end),
                            "nr": int(env.num_roads), "s": canon.state_digest(canon.oracle_state(env))}
@@ -100,6 +102,7 @@ def replay_oracle(tr, max_steps=None):
             return
         da, aa = nxt()
         obs, rew, done, info = env.step(da, aa)
+        obs = pad_obs(obs)
         got = {"r": canon.fhex(rew), "d": int(bool(done)), "o": canon.obs_digest(obs),
                "s": canon.state_digest(canon.oracle_state(env)), "_obs": obs, "_env": env, "_k": k,
                "_info": info, "_da": da, "_aa": aa}
