@@ -104,6 +104,7 @@ struct td_handle {
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
   std::string kernel_name;    // td_step_kernel_name
   std::string sel_kernel_name;  // td_step_boards_kernel_name
+  std::string list_kernel_name;  // td_step_boards_dev_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -152,6 +153,11 @@ struct td_handle {
   hipEvent_t id_ev[kIdSlots] = {};
   int id_next = 0;
   std::vector<uint8_t> id_role;  // [B] copy_check's scratch, and ids_check's: all zero between calls
+  // td_step_boards_dev, td_copy_boards_dev (td_list_check.h): the check kernel's per-board mark
+  // words, the record its verdict goes to, and the serial of the next call that launches
+  uint32_t* d_list_marks = nullptr;  // [B]
+  ListState* d_list = nullptr;       // [1]
+  long long list_calls = 0;
 };
 
 namespace {
@@ -260,7 +266,9 @@ std::vector<DevArray> dev_arrays(td_handle* h) {
           {TD_SLOT(d_epstats), 0, 2 * sizeof(double)},
           {TD_SLOT(d_lastep), sizeof(td_episode_record), 0},
           {TD_SLOT(d_guard_to), 0, w},
-          {TD_SLOT(d_pairs), 2 * sizeof(int32_t), 0}};
+          {TD_SLOT(d_pairs), 2 * sizeof(int32_t), 0},
+          {TD_SLOT(d_list_marks), w, 0},
+          {TD_SLOT(d_list), 0, sizeof(ListState)}};
 }
 #undef TD_SLOT
 
@@ -411,6 +419,22 @@ int upload_ids(td_handle* h, const int32_t* ids0, const int32_t* ids1, int n, hi
   HIP_OK(hipMemcpyAsync(h->d_pairs, stage, ids1 ? 2 * bytes : bytes, hipMemcpyHostToDevice, s));
   HIP_OK(hipEventRecord(h->id_ev[q], s));
   h->id_next = (q + 1) % kIdSlots;
+  return 0;
+}
+
+// The check of a device-resident list on the call's stream, in front of the kernel that
+// consumes it (td_list_check.hip): src == nullptr for a step's list.  The call takes the next
+// serial; its epoch stamps the marks, so the scratch is cleared only once per round of epochs.
+int enqueue_list_check(td_handle* h, const int32_t* src, const int32_t* dst, int cap, const int32_t* count,
+                       td_list_status* status, hipStream_t s) {
+  ListCheckArgs c{};
+  c.src = src; c.dst = dst; c.count = count; c.cap = cap; c.B = h->B;
+  c.call = (int)(h->list_calls & 0x7fffffff);
+  c.epoch = list_epoch(h->list_calls);
+  c.marks = h->d_list_marks; c.st = h->d_list; c.status = status;
+  if (c.epoch == 1 && h->list_calls != 0) HIP_OK(hipMemsetAsync(h->d_list_marks, 0, (size_t)h->B * sizeof(uint32_t), s));
+  HIP_OK(launch_list_check(c, s));
+  h->list_calls += 1;
   return 0;
 }
 
@@ -575,6 +599,11 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
       rc = fail("episode records init");
   }
   if (!rc && hipMemcpy(h->d_cfg, &h->dcfg, sizeof(TdDevCfg), hipMemcpyHostToDevice) != hipSuccess) rc = fail("cfg upload");
+  if (!rc) {  // no defect pending; the marks are zero: no epoch (>= 1) has marked a board
+    ListState ls{};
+    ls.key = kListNoDefect;
+    if (hipMemcpy(h->d_list, &ls, sizeof ls, hipMemcpyHostToDevice) != hipSuccess) rc = fail("list record init");
+  }
   for (int q = 0; q < kSideStreams && !rc; ++q) {  // side streams (layout refills)
     const hipError_t e = hipStreamCreateWithFlags(&h->side[q], hipStreamNonBlocking);
     if (e != hipSuccess) rc = fail("side stream: %s", hipGetErrorString(e));
@@ -1007,6 +1036,82 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
     for (int i = 0; !known && i < n; ++i) h->ledger.mark(boards[i]);  // written whole just now
   guard.ok = true;
   return 0;
+}
+
+// td_step_boards for a list, its length and its verdict in device memory: the host checks what it
+// can see (the io, cap, the handle's settings), the check kernel the contents, on the stream in
+// front of the list kernel; nothing is brought to the host and nothing is waited for.
+int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards_dev, int cap, const int32_t* count_dev,
+                       td_list_status* status_dev, void* stream) {
+  // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
+  if (io && io->size == (uint32_t)sizeof(td_step_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
+    return fail("td_step_boards_dev: cap = %d is negative", cap);
+  if (check_step_io("td_step_boards_dev", h, io)) return -1;
+  if (h->frame_skip > 1)
+    return fail("td_step_boards_dev: not supported with frame skip (td_frame_skip() = %d); set td_set_frame_skip(h, 1) "
+                "first", h->frame_skip);
+  if (h->opp_np && h->autoreset)
+    return fail("td_step_boards_dev: not supported with random_agent = 0 and auto-reset on (the reset kernel behind a "
+                "step goes by done[] of every board, and an unnamed board's is stale)");
+  if (cap > h->B) return fail("td_step_boards_dev: cap = %d outside [0, %d] (the handle's boards)", cap, h->B);
+  if (cap == 0) return 0;
+  if (!boards_dev) return fail("td_step_boards_dev: boards_dev is NULL with cap = %d", cap);
+  hipStream_t s = (hipStream_t)stream;
+  StepArgs a = step_args(h, io);
+  // td_retain_obs: which boards the list names is not known here, so the kernel skips clean
+  // windows only if every board's row is known, and no board is marked afterwards
+  a.obs_skip = h->ledger.list_step_skips(io->obs) ? 1 : 0;
+  ObsLedger::Guard guard{&h->ledger};
+  // on the stream: the refill and the ring guard, then the check, then the kernel
+  if (before_step_launch(h, a, s) || enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
+  const EvPair ev = next_timing_pair(h);  // the consumer's, whatever `every` is (as td_step_boards')
+  HIP_OK(launch_step_list(a, boards_dev, cap, count_dev, &h->d_list->verdict, s, ev.e0, ev.e1));
+  h->steps += 1;
+  h->since_guard += 1;
+  h->ledger.list_call_into(io->obs);
+  guard.ok = true;
+  return 0;
+}
+
+// td_copy_boards for lists, their length and their verdict in device memory (see above).
+int td_copy_boards_dev(td_handle* h, const int32_t* src_dev, const int32_t* dst_dev, int cap, const int32_t* count_dev,
+                       float* obs, td_list_status* status_dev, void* stream) {
+  if (cap < 0) return fail("td_copy_boards_dev: cap = %d is negative", cap);  // (needs no handle)
+  if (!h) return fail("td_copy_boards_dev: NULL handle");
+  if (cap > h->B) return fail("td_copy_boards_dev: cap = %d outside [0, %d] (the handle's boards)", cap, h->B);
+  if (cap == 0) return 0;
+  if (!src_dev || !dst_dev) return fail("td_copy_boards_dev: src_dev or dst_dev is NULL with cap = %d", cap);
+  hipStream_t s = (hipStream_t)stream;
+  ObsLedger::Guard guard{&h->ledger};
+  if (enqueue_list_check(h, src_dev, dst_dev, cap, count_dev, status_dev, s)) return -1;
+  StepArgs a = base_args(h);
+  a.obs = obs;
+  const EvPair ev = next_timing_pair(h);
+  HIP_OK(launch_copy_list(a, src_dev, dst_dev, cap, count_dev, &h->d_list->verdict, s, ev.e0, ev.e1));
+  // the destinations' states change: into the retained buffer the known boards stay known (their
+  // rows were rewritten whole), any other buffer (or none) leaves it behind
+  h->ledger.list_call_into(obs);
+  guard.ok = true;
+  return 0;
+}
+
+int td_list_errors(td_handle* h, td_list_status* first, int clear) {
+  if (!h) return fail("td_list_errors: NULL handle");
+  ListState ls;
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(&ls, h->d_list, sizeof ls, hipMemcpyDeviceToHost));
+  if (first) *first = ls.refused ? ls.first : td_list_status{0, 0, 0, 0};
+  if (clear && ls.refused) {  // (key, arrived and verdict belong to the kernels)
+    HIP_OK(hipMemset(&h->d_list->refused, 0, sizeof ls.refused));
+    HIP_OK(hipMemset(&h->d_list->first, 0, sizeof ls.first));
+  }
+  return (int)std::min<uint32_t>(ls.refused, 0x7fffffffu);
+}
+
+const char* td_step_boards_dev_kernel_name(td_handle* h) {
+  if (!h) return "";
+  h->list_kernel_name = kernel_display_name(list_row(base_args(h)));
+  return h->list_kernel_name.c_str();
 }
 
 const char* td_step_boards_kernel_name(td_handle* h) {

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "td_common.h"
+#include "td_list_check.h"
 #include "../../include/tdstep.h"
 
 namespace td {
@@ -113,6 +114,10 @@ KernelRow skip_row_f32(const StepArgs& a);
 KernelRow skip_row_f16(const StepArgs& a);
 KernelRow sel_row_f32(const StepArgs& a);
 KernelRow sel_row_f16(const StepArgs& a);
+// The partial step whose list, count and verdict are read from device memory
+// (td_step_boards_dev; td_step_list.hip, td_step_list_f16.hip): one kernel per row, as sel_row_*.
+KernelRow list_row_f32(const StepArgs& a);
+KernelRow list_row_f16(const StepArgs& a);
 
 // TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
 hipError_t launch_reset(const StepArgs& a, hipStream_t s);
@@ -134,6 +139,15 @@ hipError_t launch_opponent(const StepArgs& a, int side, int level, hipStream_t s
 // ev0 / ev1: optional timing events bound to the kernel's dispatch, as launch_step's.
 hipError_t launch_copy(const StepArgs& a, const int32_t* pairs, int n, hipStream_t s, hipEvent_t ev0 = nullptr,
                        hipEvent_t ev1 = nullptr);
+// The same copy for a device-resident list (td_copy_boards_dev): boards dst[i] become copies of
+// boards src[i] for i < *count (count == nullptr: cap), unless verdict->code says the list was
+// refused (td_list_check.hip, launched in front): then no wave reads or writes anything of any
+// board.  One block per entry of cap.
+hipError_t launch_copy_list(const StepArgs& a, const int32_t* src, const int32_t* dst, int cap, const int32_t* count,
+                            const td_list_status* verdict, hipStream_t s, hipEvent_t ev0 = nullptr,
+                            hipEvent_t ev1 = nullptr);
+// The check of a device-resident list (td_list_check.hip): one thread per entry of a.cap >= 1.
+hipError_t launch_list_check(const ListCheckArgs& a, hipStream_t s);
 
 // Legal-action masks of the boards' present state (td_action_mask; td_mask.hip): which
 // action the next step would execute.  Reads the header, the cell words (map[6] in bits

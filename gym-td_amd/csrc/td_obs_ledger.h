@@ -59,6 +59,21 @@ struct ObsLedger {
     for (int i = 0; known && !retained_valid && i < n; ++i) known = obs_known[(size_t)boards[i]] != 0;
     return known;
   }
+  // Device-resident lists (td_step_boards_dev, td_copy_boards_dev): the host does not know
+  // which boards a call names, nor whether the device will accept the list, so these never
+  // mark a board: no sequence of them raises n_known or sets retained_valid.
+  // A step of a device list into `obs` may skip only if every board is known.
+  bool list_step_skips(const void* obs) const { return full_step_skips(obs); }
+  // After such a step, or a device-list copy, into `obs` (nullptr: a copy without rows).  Into
+  // the retained buffer the set of known boards stays as it was: a known board's row was
+  // written whole or in its dirty windows, an unknown one's whole, but which cannot be marked;
+  // a refused list changed nothing.  Any other buffer leaves the retained one behind, as the
+  // host-list forms do.  Whether `obs` is the retained buffer.
+  bool list_call_into(const void* obs) {
+    const bool mine = is_retained(obs);
+    if (!mine) touch();
+    return mine;
+  }
   // The block [p, p + bytes) was freed (a record of no size counts as one byte): a later
   // allocation may reuse the address, which must not be taken for the retained buffer.
   // Whether the retention was dropped.

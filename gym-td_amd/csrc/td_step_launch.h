@@ -74,10 +74,11 @@ KernelRow select_step_row(const StepArgs& a, int kind) {
   });
 }
 
-// The three families in the format a.obs_f16.
+// The four families in the format a.obs_f16.
 inline KernelRow step_row(const StepArgs& a, int kind) { return a.obs_f16 ? step_row_f16(a, kind) : step_row_f32(a, kind); }
 inline KernelRow skip_row(const StepArgs& a) { return a.obs_f16 ? skip_row_f16(a) : skip_row_f32(a); }
 inline KernelRow sel_row(const StepArgs& a) { return a.obs_f16 ? sel_row_f16(a) : sel_row_f32(a); }
+inline KernelRow list_row(const StepArgs& a) { return a.obs_f16 ? list_row_f16(a) : list_row_f32(a); }
 
 // One block of k.threads per grid entry; args: the kernel's arguments, in order.  ev0 / ev1
 // (optional): timing events bound to the kernel's own dispatch (hipExtLaunchKernel), so their
@@ -123,6 +124,16 @@ inline hipError_t launch_step_sel(const StepArgs& a, const int32_t* ids, int n, 
                                   hipEvent_t ev1 = nullptr) {
   void* args[] = {const_cast<StepArgs*>(&a), &ids, &n};
   return launch_row(sel_row(a), n, args, s, ev0, ev1);
+}
+
+// The partial step of a device-resident list (td_step_boards_dev): boards ids[0 .. *count) (count ==
+// nullptr: cap), unless verdict->code says the check kernel launched in front refused the list.
+// One block per entry of cap >= 1: the host does not know the count.
+inline hipError_t launch_step_list(const StepArgs& a, const int32_t* ids, int cap, const int32_t* count,
+                                   const td_list_status* verdict, hipStream_t s, hipEvent_t ev0 = nullptr,
+                                   hipEvent_t ev1 = nullptr) {
+  void* args[] = {const_cast<StepArgs*>(&a), &ids, &cap, &count, &verdict};
+  return launch_row(list_row(a), cap, args, s, ev0, ev1);
 }
 
 // Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute units:

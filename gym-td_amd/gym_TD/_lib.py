@@ -55,6 +55,15 @@ class TdStepIO(ctypes.Structure):
         super().__init__(**kw)
 
 
+class TdListStatus(ctypes.Structure):
+    """struct td_list_status (tdstep.h): the verdict of a device-list call, 16 bytes."""
+    _fields_ = [("code", ctypes.c_int32), ("call", ctypes.c_int32), ("entry", ctypes.c_int32),
+                ("board", ctypes.c_int32)]
+
+
+LIST_OK, LIST_BAD_COUNT, LIST_RANGE, LIST_TWICE, LIST_OVERLAP = range(5)
+
+
 class TdMaskIO(ctypes.Structure):
     """struct td_mask_io (tdstep.h): the size / ABI header, the three device outputs, the row pitch."""
     _fields_ = [("size", ctypes.c_uint32), ("abi", ctypes.c_uint32), ("def_mask", c_vp), ("def_code", c_vp),
@@ -97,6 +106,9 @@ def _load():
         "td_copy_boards": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp]),
         "td_step": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp]),
         "td_step_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp, ctypes.c_int, c_vp]),
+        "td_step_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdStepIO), c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+        "td_copy_boards_dev": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, c_vp, c_vp, c_vp, c_vp]),
+        "td_list_errors": (ctypes.c_int, [c_vp, ctypes.POINTER(TdListStatus), ctypes.c_int]),
         "td_mask_io_init": (None, [ctypes.POINTER(TdMaskIO)]),
         "td_action_mask": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
@@ -121,6 +133,7 @@ def _load():
         "td_retained_step_kernel": (ctypes.c_int, [c_vp]),
         "td_step_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_step_boards_kernel_name": (ctypes.c_char_p, [c_vp]),
+        "td_step_boards_dev_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_config_epoch": (ctypes.c_int, [c_vp]),
         "td_kernel_timing": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int]),
         "td_kernel_times": (ctypes.c_int, [c_vp, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),

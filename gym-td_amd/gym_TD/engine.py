@@ -402,13 +402,49 @@ class TDEngine(object):
         One kernel on torch's current stream, which must be the stream of step(); nothing is
         synchronised (with ``host_io`` the call waits for the kernel, as ``step()`` does).  An
         empty list is a no-op.  TDError, with nothing changed: an id out of range or named
-        twice, ``frame_skip`` > 1, random_agent=False with auto-reset on."""
+        twice, ``frame_skip`` > 1, random_agent=False with auto-reset on.
+        Ids that are on the device already: ``step_boards_dev`` (no copy to the host, no wait)."""
         return self._launch_step(def_act, atk_act, _board_ids(boards))
 
-    def _launch_step(self, def_act, atk_act, ids=None):
-        """step() (ids None) or step_boards(): stage the actions, launch, hand out the tensors."""
+    def step_boards_dev(self, boards, def_act=None, atk_act=None, count=None, status=None):
+        """``step_boards`` for ids that are on the device (td_step_boards_dev): nothing is copied
+        to the host and nothing is waited for -- the list is validated by a kernel on the
+        stream, in front of the step's.
+
+        ``boards``: an integer tensor on the engine's device (int32 and contiguous is taken as
+        it is, any other integer tensor is converted on the device); its length is the call's
+        ``cap``.  A CPU tensor, list or numpy array raises ValueError: that is ``step_boards``.
+        ``count``: None (every entry is used) or a one-element int32 device tensor: the first
+        ``count[0]`` entries are used, the rest is never read as ids -- compact "the boards
+        that are not done" into a buffer of fixed size and pass its length here.
+        ``status``: an optional int32 device tensor of 4 elements, receives the call's verdict
+        (code, call, entry, board; code 0 = accepted) in stream order.
+
+        A list the device refuses (a count outside [0, cap], an id out of range, a board named
+        twice) changes nothing at all; ``list_errors()`` tells afterwards.  TDError at once, with
+        nothing changed: more ids than boards, ``frame_skip`` > 1, random_agent=False with
+        auto-reset on.  With ``retain_obs`` clean windows are skipped only while every board's
+        row is known.  The tensors stay alive until the next call; with ``host_io`` the call
+        waits for the kernel, as ``step()`` does.  Returns (obs, reward, done)."""
+        ids = _dev_ids(boards, self.device, "step_boards")
+        dev = (ids, _dev_words(count, 1, self.device, "count"), _dev_words(status, 4, self.device, "status"))
+        return self._launch_step(def_act, atk_act, None, dev)
+
+    def _call_step(self, io, ids, dev):
+        if dev is not None:
+            b, c, st = dev
+            return _lib.lib.td_step_boards_dev(self._h, io, b.data_ptr(), int(b.numel()),
+                                               c.data_ptr() if c is not None else None,
+                                               st.data_ptr() if st is not None else None, self._stream())
+        if ids is None:
+            return _lib.lib.td_step(self._h, io, self._stream())
+        return _lib.lib.td_step_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream())
+
+    def _launch_step(self, def_act, atk_act, ids=None, dev=None):
+        """step() (ids None), step_boards() or step_boards_dev() (dev: the id, count and status
+        tensors): stage the actions, launch, hand out the tensors."""
         io = self._io
-        keep = []
+        keep = [t for t in dev if t is not None] if dev is not None else []
         if self.host_io:
             if self.mode != "atk":
                 self._def_np[...] = np.asarray(def_act, dtype=np.int64).reshape(self._def_np.shape)
@@ -416,8 +452,7 @@ class TDEngine(object):
             if self.mode != "def":
                 self._atk_np[...] = np.asarray(atk_act, dtype=np.int64).reshape(self._atk_np.shape)
                 io.atk_act = self._atk_in.data_ptr()
-            _lib.check(_lib.lib.td_step(self._h, io, self._stream()) if ids is None else
-                       _lib.lib.td_step_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
+            _lib.check(self._call_step(io, ids, dev))
             # the outputs are the caller's as soon as this returns, and the next call
             # rewrites the staged actions: wait for the kernel
             torch.cuda.current_stream(self.device).synchronize()
@@ -435,9 +470,8 @@ class TDEngine(object):
                 raise ValueError("attacker action must have shape (B, 3, 8)")
             keep.append(a)
             io.atk_act = a.data_ptr()
-        _lib.check(_lib.lib.td_step(self._h, io, self._stream()) if ids is None else
-                   _lib.lib.td_step_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
-        self._keep = keep  # actions stay alive until the next call
+        _lib.check(self._call_step(io, ids, dev))
+        self._keep = keep  # actions (and a device list) stay alive until the next call
         return self.obs, self.reward, self.done
 
     def copy_boards(self, src, dst, write_obs=True):
@@ -460,13 +494,54 @@ class TDEngine(object):
         into ``self.obs`` (the rows of the sources' present states); without it nothing is
         written and the next step writes every byte.  The engine's other last-step tensors
         (``reward``, ``done``, the info tensors) keep ``dst``'s old rows until the next step.
-        Returns ``self.obs``."""
+        Returns ``self.obs``.
+        Ids that are on the device already: ``copy_boards_dev`` (no copy to the host, no wait)."""
         s, d = _board_ids(src), _board_ids(dst)
         if s.shape != d.shape:
             raise ValueError("src and dst must name equally many boards, got %d and %d" % (s.size, d.size))
         _lib.check(_lib.lib.td_copy_boards(self._h, s.ctypes.data, d.ctypes.data, int(s.size),
                                            self.obs.data_ptr() if write_obs else None, self._stream()))
         return self.obs
+
+    def copy_boards_dev(self, src, dst, count=None, write_obs=True, status=None):
+        """``copy_boards`` for ids that are on the device (td_copy_boards_dev): nothing is copied
+        to the host and nothing is waited for; the lists are validated by a kernel on the
+        stream, in front of the copy's.
+
+        ``src`` / ``dst``: integer tensors of one length on the engine's device (int32 and
+        contiguous is taken as it is); ``count`` and ``status`` as in ``step_boards_dev``.  A CPU
+        tensor, list or numpy array raises ValueError: that is ``copy_boards``.  A list the
+        device refuses (a bad count, an id out of range, a board twice in ``dst`` or in both)
+        changes nothing; ``list_errors()`` tells afterwards.  The tensors stay alive until the
+        next call.  Returns ``self.obs``."""
+        s = _dev_ids(src, self.device, "copy_boards")
+        d = _dev_ids(dst, self.device, "copy_boards")
+        if s.numel() != d.numel():
+            raise ValueError("src and dst must name equally many boards, got %d and %d" % (s.numel(), d.numel()))
+        c = _dev_words(count, 1, self.device, "count")
+        st = _dev_words(status, 4, self.device, "status")
+        _lib.check(_lib.lib.td_copy_boards_dev(self._h, s.data_ptr(), d.data_ptr(), int(s.numel()),
+                                               c.data_ptr() if c is not None else None,
+                                               self.obs.data_ptr() if write_obs else None,
+                                               st.data_ptr() if st is not None else None, self._stream()))
+        self._keep_list = (s, d, c, st)  # alive until the next call's kernels are behind them on the stream
+        if self.host_io:
+            torch.cuda.current_stream(self.device).synchronize()
+        return self.obs
+
+    def list_errors(self, clear=True):
+        """Device-list calls (``step_boards_dev``, ``copy_boards_dev``) whose list the device
+        refused since the last clear (td_list_errors; waits for the device): ``(n_refused,
+        first)``, ``first`` None or a dict with ``code`` (1 count, 2 range, 3 twice, 4 overlap),
+        ``call`` (the call's serial), ``entry`` and ``board``."""
+        rec = _lib.TdListStatus()
+        n = _lib.check(_lib.lib.td_list_errors(self._h, _lib.ctypes.byref(rec), int(bool(clear))))
+        first = dict(code=rec.code, call=rec.call, entry=rec.entry, board=rec.board) if n else None
+        return n, first
+
+    def step_boards_dev_kernel_name(self):
+        """The kernel ``step_boards_dev`` launches behind its check (td_step_boards_dev_kernel_name)."""
+        return _lib.lib.td_step_boards_dev_kernel_name(self._h).decode()
 
     def action_mask(self, code=False):
         """Legal-action masks of every board's present state (td_action_mask): what the next
@@ -708,6 +783,28 @@ def _board_ids(x):
     if a.size and (int(a.min()) < -2 ** 31 or int(a.max()) >= 2 ** 31):
         raise ValueError("board id out of range")
     return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _dev_ids(x, device, host_method):
+    """Board ids on the engine's device -> contiguous int32 device tensor, without a copy to the host."""
+    if not isinstance(x, torch.Tensor) or x.device != device:
+        raise ValueError("board ids must be an integer tensor on %s; for ids on the host use %s()" % (device, host_method))
+    if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+        raise ValueError("board ids must be integers, not %s" % x.dtype)
+    x = x.detach().reshape(-1)
+    if x.dtype != torch.int32 or not x.is_contiguous():
+        x = x.to(torch.int32).contiguous()
+    return x
+
+
+def _dev_words(x, n, device, what):
+    """None, or an int32 device tensor of n elements (count, status), taken as it is."""
+    if x is None:
+        return None
+    if not isinstance(x, torch.Tensor) or x.device != device or x.dtype != torch.int32 or x.numel() != n \
+            or not x.is_contiguous():
+        raise ValueError("%s must be a contiguous int32 tensor of %d element(s) on %s" % (what, n, device))
+    return x
 
 
 def _as_dev(x, dtype, device):

@@ -386,6 +386,22 @@ class TDVecEnv(object):
         fork the leaves, step the leaves, read their rows and masks."""
         return self._step(actions, lambda **kw: self.engine.step_boards(boards, **kw))
 
+    def fork_dev(self, src, dst, count=None, status=None):
+        """fork() for env ids that are on the device (TDEngine.copy_boards_dev): integer device
+        tensors, an optional one-element int32 ``count`` tensor and a 4-element int32
+        ``status`` tensor for the verdict; nothing is copied to the host or waited for.  A list
+        the device refuses changes nothing (``engine.list_errors()``)."""
+        obs = self.engine.copy_boards_dev(src, dst, count=count, status=status)
+        if self.with_action_mask:
+            self._masks = self.engine.action_mask()
+        return obs
+
+    def step_boards_dev(self, boards, actions, count=None, status=None):
+        """step_boards() for env ids that are on the device (TDEngine.step_boards_dev): with
+        fork_dev() a search iteration without a host round trip.  ``count`` / ``status`` as in
+        fork_dev(); with ``action_mask=True`` the masks are computed again."""
+        return self._step(actions, lambda **kw: self.engine.step_boards_dev(boards, count=count, status=status, **kw))
+
     def _step(self, actions, run):
         if self.mode == "def":
             obs, rew, done = run(def_act=actions)

@@ -403,6 +403,79 @@ int td_step(td_handle* h, const td_step_io* io, void* stream);
  *   goes by done[] of every board, and an unnamed board's is stale). */
 int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, int n, void* stream);
 
+/* Device-resident board lists: td_step_boards and td_copy_boards for a search whose ids are on
+ * the device already (the argmax of a score, "every board that is not done", the best k of a
+ * population), with no copy to the host, no wait for the stream and no O(n) host check.  The
+ * list and its length are read from device memory; the validation runs in a kernel on the
+ * step's stream (td_list_check_kernel) in front of the kernel that consumes the list; a list
+ * the device refuses makes every wave of that kernel exit before it reads or writes anything of
+ * any board, and the refusal is reported after the fact (status_dev, td_list_errors).
+ * For a list the device accepts the result is byte for byte what td_step_boards /
+ * td_copy_boards give for the same ids: board state, both RNG streams, flags, every output row,
+ * the episode statistics and records.  io, obs, the outputs and the kernel shape (one wave per
+ * list entry in TD_KERNEL_LARGE's shape; td_step_boards_dev_kernel_name) are those of the
+ * host-list forms, and so is the accounting: a call counts as a launch for the refill cadence
+ * and the ring guard, and its consumer kernel takes the next td_kernel_timing pair.
+ * boards_dev / src_dev / dst_dev: cap int32 ids in device memory.
+ * count_dev: device memory, may be NULL = cap entries are used.  Otherwise the first *count_dev
+ *   entries are used, which must lie in [0, cap]; entries at or past the count are never read
+ *   as ids, whatever they hold -- a caller compacts "the boards that are not done" into a
+ *   buffer of fixed size without learning the count on the host.  The grid is cap either way.
+ * Lifetime of the id memory: what these pointers name must be final, in stream order, before
+ *   the call (written by earlier work on `stream`, or complete on the host's side), and must
+ *   stay unchanged until the call's kernels have run; work enqueued on the same stream after
+ *   the call may reuse it.
+ * status_dev (device, may be NULL): the call's verdict, written on every call that launches,
+ *   code = TD_LIST_OK on success.  call: the 0-based serial of the device-list calls of this
+ *   handle that launched (a call refused on the host, or with cap == 0, has no serial).  code:
+ *   the lowest-numbered defect class present in the list.  entry / board: one list entry that
+ *   shows that defect and the id it holds (for TD_LIST_TWICE and TD_LIST_OVERLAP any one of the
+ *   entries that name the board); for TD_LIST_BAD_COUNT entry is -1 and board the count read.
+ * Refused on the host (< 0, td_last_error, nothing enqueued, nothing changed): a NULL io or a
+ *   bad size / abi word, then a NULL handle, in td_step's order and with the call's own name;
+ *   missing required pointers; a NULL id array with cap > 0; cap < 0 (needs no handle: checked
+ *   with the io words) or cap > the handle's boards; for the step td_frame_skip() > 1 and
+ *   random_agent = 0 with auto-reset on, for td_step_boards' reasons.  cap == 0 returns 0 and
+ *   launches nothing.
+ * Refused on the device -- everything about the contents: a count outside [0, cap]
+ *   (TD_LIST_BAD_COUNT); an id outside [0, boards) (TD_LIST_RANGE); a board named twice in
+ *   boards or in dst (TD_LIST_TWICE); a board named in both src and dst (TD_LIST_OVERLAP).  A
+ *   board repeated in src is fine, as in td_copy_boards.  Then nothing changes: no board, flag,
+ *   stream, output row, observation byte, retained window, episode statistic or record.  (The
+ *   side refill and the ring guard in front of a step launch may still have run; they never
+ *   change a result.)  The call itself returned 0: read status_dev in stream order, or ask
+ *   td_list_errors.
+ * Retained observation: the host does not know which boards a call names.  A step into
+ *   td_retained_obs(h) skips clean windows only if EVERY board's row is known; where the set
+ *   was not complete the named rows are written whole, but the set of known boards stays as it
+ *   was.  A copy into the retained buffer leaves the set unchanged too (a known destination's
+ *   row was just rewritten whole, an unknown one stays unknown).  A step or copy into any other
+ *   buffer, and a copy with obs == NULL, leaves the retained buffer behind (the next step into
+ *   it writes every byte), as the host-list forms do -- even if the device then refuses the
+ *   list; that costs one full write.  A device refusal never makes the handle claim more than
+ *   it did.
+ * Asynchronous on `stream`, which must be the step's stream. */
+enum td_list_code { TD_LIST_OK = 0, TD_LIST_BAD_COUNT = 1, TD_LIST_RANGE = 2, TD_LIST_TWICE = 3, TD_LIST_OVERLAP = 4 };
+typedef struct td_list_status { int32_t code, call, entry, board; } td_list_status; /* 16 B */
+int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards_dev, int cap,
+                       const int32_t* count_dev, td_list_status* status_dev, void* stream);
+/* td_copy_boards for a device-resident list: board dst_dev[i] becomes board src_dev[i] for the
+ * entries used, obs as in td_copy_boards.  Everything else -- cap and count_dev, the lifetime
+ * of the id memory, status_dev, the refusal split between host (a NULL handle, NULL arrays
+ * with cap > 0, cap < 0 or > the handle's boards) and device (TD_LIST_BAD_COUNT, TD_LIST_RANGE,
+ * TD_LIST_TWICE in dst, TD_LIST_OVERLAP of src and dst), the retained-observation rules (the
+ * set of known boards is unchanged by a copy into td_retained_obs(h); any other obs, NULL
+ * included, leaves the retained buffer behind) and the td_kernel_timing pair -- is as the
+ * comment above td_step_boards_dev says.  Asynchronous on `stream`, the step's stream. */
+int td_copy_boards_dev(td_handle* h, const int32_t* src_dev, const int32_t* dst_dev, int cap,
+                       const int32_t* count_dev, float* obs, td_list_status* status_dev, void* stream);
+/* How many device-list calls (td_step_boards_dev, td_copy_boards_dev) the device refused since
+ * the last clear, and in *first (may be NULL) the record of the first of them; with no refusal
+ * *first is all zero (code = TD_LIST_OK).  clear != 0 zeroes the count and the record.  Waits
+ * for the device's work first -- synchronous, the pattern of td_guard_timeouts: a search loop
+ * asks once in a while, not per call. */
+int td_list_errors(td_handle* h, td_list_status* first, int clear);
+
 /* Legal-action masks: for every board and every action, whether the NEXT td_step would
  * execute that action if it were the only thing asked of that side -- decided on the device
  * from the board's present state with the step's own comparisons, so a policy can sample
@@ -488,6 +561,10 @@ const char* td_step_kernel_name(td_handle* h);
  * "td_step_sel_kernel_f16<...>" with TD_OBS_F16: one wave per named board in TD_KERNEL_LARGE's
  * shape, whatever kind td_step launches.  The string is the handle's, valid until the next call. */
 const char* td_step_boards_kernel_name(td_handle* h);
+/* The kernel td_step_boards_dev launches behind its check kernel: "td_step_list_kernel<10, 0,
+ * false>" or "td_step_list_kernel_f16<...>", the same rows and shape as td_step_boards'.  The
+ * string is the handle's, valid until the next call. */
+const char* td_step_boards_dev_kernel_name(td_handle* h);
 
 /* Steps between launches of the layout refill kernel on the side streams (auto-reset;
  * default 64, 0 = none).  A pure performance knob: before every 15th step (and the first
