@@ -1,12 +1,13 @@
 // td_board.h -- board rules and observation encoding of the step kernels (td_step_*.h):
 // fail codes, the tower nibble of an LDS cell word, Chebyshev distance, Enemy.damage, the
-// binary / broadcast / distance / enemy channel classes of the (45, L, L) observation, the
+// cell bits of the (45, L, L) observation's binary channels (their classes: td_obs_win.h), the
 // dry-ring wait and the kernarg-segment read of the step arguments.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "td_common.h"
 #include "td_kernels.h"
+#include "td_obs_win.h"
 #include "td_wave.h"
 
 namespace td {
@@ -73,11 +74,7 @@ __device__ __forceinline__ double damage(double LP, double atk, double def, bool
   return LP;
 }
 
-// Binary observation channels as bits of one word per cell (bit c = channel c):
-// 0-3 roads, 4 end, 6-8 starts, 14 buildable (map[6] == 0), 15-16 tower level,
-// 17-20 tower type (TDBoard.py:113-133).
-constexpr uint32_t kBinaryChannels = 0x1FC1DFu;
-
+// (kBinaryChannels, bit c = channel c: td_obs_win.h)
 __device__ __forceinline__ uint32_t cell_bits(uint32_t w, uint32_t tw) {
   uint32_t m = (w & 0x1Fu) | (((w >> 5) & 7u) << 6) | ((w >> 24) == 0u ? (1u << 14) : 0u);
   if (tw & 0x80u) m |= (1u << (15u + ((tw >> 2) & 1u))) | (1u << (17u + (tw & 3u)));
@@ -90,42 +87,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-
-// Channel kinds of the observation (TDBoard.get_states, :112-143).
-enum ObsKind : int { OK_BIN, OK_CONST, OK_D9, OK_ENEMY };
-__host__ __device__ constexpr int obs_kind(int ch) {
-  return ch == 9 ? OK_D9
-       : (ch < 32 && ((kBinaryChannels >> ch) & 1u)) ? OK_BIN
-       : (ch >= 25 && ch < 41) ? OK_ENEMY
-       : OK_CONST;
-}
-
-// Channel classes of the observation as 64-bit channel masks (TDBoard.get_states,
-// :112-143): bits of the packed cell word, the enemy_LP planes, channel 9 (distance
-// by table), and the broadcast channels.
-constexpr uint64_t kChBin = kBinaryChannels;
-constexpr uint64_t kChD9 = 1ull << 9;
-constexpr uint64_t kChEnemy = 0xFFFFull << 25;
-constexpr uint64_t kChAll = (1ull << NCH) - 1;
-constexpr uint64_t kChConst = kChAll & ~(kChBin | kChD9 | kChEnemy);
-
-// Dirty classes of the observation (td_retain_obs): the channels of one class change
-// together, and a step that found none of a window's classes dirty leaves the window as
-// its last write left it.  STATIC: the layout (roads, end, starts, distance, channel 10),
-// new only with a new episode; LP: channel 5 (a leak); TOWER: buildable, tower level / type
-// (the tower list changed); COST: channels 21-24 (cost_def crossed a tower cost); ENEMY:
-// the enemy planes (an enemy before or after the step); ALWAYS: costs, progress, channels
-// 41-44.
-enum : uint32_t { OD_STATIC = 1u, OD_LP = 2u, OD_TOWER = 4u, OD_COST = 8u, OD_ENEMY = 16u, OD_ALWAYS = 32u, OD_ALL = 63u };
-__host__ __device__ constexpr uint32_t obs_dirty_class(int ch) {
-  return ch == 5 ? OD_LP
-       : (ch <= 10) ? OD_STATIC
-       : (ch <= 13) ? OD_ALWAYS
-       : (ch <= 20) ? OD_TOWER
-       : (ch <= 24) ? OD_COST
-       : (ch <= 40) ? OD_ENEMY
-       : OD_ALWAYS;
-}
 
 // The step wave of board b found layout `head` unpublished at the episode end.  If a
 // refill wave holds the board's claim it is drawing exactly this layout (an empty ring

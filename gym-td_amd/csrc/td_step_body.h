@@ -241,6 +241,11 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
   }
   if (refill && x.lane < HOT_CACHE) sst(&hot[4 + x.lane], R.cache);
   const uint32_t dirty = obs_dirty(S, u, C, a.obs_skip != 0, was_reset);
+  // the channels the written windows read (both waves'): what channel_scalars must provide
+  uint64_t need = kChAll;
+  if constexpr (LT != 0) {
+    if ((reinterpret_cast<uintptr_t>(a.obs) & (ObsFmt<OT>::UB - 1)) == 0) need = obs_need<LT, OT>(obs, dirty);
+  }
   if constexpr (SPLIT) {
     // (B) the second wave's early pass has landed; it takes the board and the outputs
     // and stores them while this wave computes the statistics and broadcast channels;
@@ -257,7 +262,7 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     }
     __syncthreads();
     enemy_stats(S, u, x);  // no-op for a board without enemies (e.g. just reset)
-    channel_scalars(S, u, x);
+    channel_scalars(S, u, x, need);
     __syncthreads();
     if (was_reset) write_obs_lines<NC, LT, 0, -1, 4, 0, OT>(S, x.lane, obs, u.n > 0, wt, a.edge_wt);
     // (every class dirty -- a step that may not skip: the writer without the skip's table reads
@@ -266,7 +271,7 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
     else write_obs_lines<NC, LT, 0, obs_late_half<LT, OT>(), 4, 2, OT, true>(S, x.lane, obs, u.n > 0, wt, a.edge_wt, dirty);
   } else {
     enemy_stats(S, u, x);  // no-op for a board without enemies (e.g. just reset)
-    channel_scalars(S, u, x);
+    channel_scalars(S, u, x, need);
     if (was_reset) {  // the new episode's layout
       store_cells(S, u, x, a, b);
       pack_obs_cells(S, x);

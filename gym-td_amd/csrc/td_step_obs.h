@@ -2,7 +2,7 @@
 // What belongs here: the group statistics and broadcast channels the planes are made of
 // (enemy_stats, d9_table, channel_scalars, pack_obs_cells, obs_value), the output formats
 // (ObsFmt), the two writers (write_obs per element, write_obs_lines in line-aligned
-// windows, with its window table ObsWinTab), the split of the windows between the two
+// windows, by the window tables of td_obs_win.h), the split of the windows between the two
 // waves of a board (obs_half, obs_late_half), the dirty classes of a retained observation
 // (cost_bits, obs_dirty) and a reset board's first observation (reset_obs).
 #pragma once
@@ -81,24 +81,38 @@ __device__ __forceinline__ void d9_table(Smem<NC>& S, int maxdist, int lane) {
   if (lane <= maxdist) S.d9[lane] = f32(ddiv((double)lane, (double)(maxdist + 1)));
 }
 
-// Broadcast channels and the channel-9 table (TDBoard.py:115-142).  (The same divisions
-// as two uniform passes over all lanes instead of a branch per channel measured slower:
-// 219 vs 214 us at 65,536 boards, profiles/r03/s24.)
+// Broadcast channels and the channel-9 table (TDBoard.py:115-142).  Lane l holds channel
+// l.  One division sequence per dependency level: every lane picks its own channel's
+// operands (1 / 1 where the channel has no quotient) and the wave divides once -- channels
+// 5, 11, 12 and the first quotient of 41-44 -- then the four lanes of 41-44 divide by
+// max_cluster_length.  (A branch per channel ran five sequences one after another; the
+// retained step is bound by the vector unit, where a sequence costs the same for one lane
+// as for 64.  While the step was bound by its 18-KB store stream the two forms measured
+// 219 vs 214 us at 65,536 boards, profiles/r03/s24.)  Each quotient is one correctly-rounded
+// f64 division, rounded once to f32, as before.
+// need: the channels the board's written windows read (ObsWinTab::ntab, obs_need): the
+// channel-9 table is built only when channel 9 is among them -- a new episode, a step that
+// may not skip, and one line misalignment in eight.
 template <int NC>
-__device__ __forceinline__ void channel_scalars(Smem<NC>& S, const U& u, const Ctx& x) {
+__device__ __forceinline__ void channel_scalars(Smem<NC>& S, const U& u, const Ctx& x, uint64_t need = kChAll) {
   const TdDevCfg& C = x.C;
   const int l = x.lane;
   if (l < 48) {
+    const bool is5 = l == 5, isq = l >= 41 && l < 45;
+    const bool isdiv = is5 || l == 11 || l == 12 || isq;
+    double num = l == 12 ? u.cost_atk : u.cost_def, den = u.max_cost;
+    if (is5) { num = (double)u.base_LP; den = (double)u.max_base_LP; }
+    if (isq) den = C.e_cost[l - 41][0];
+    if (!isdiv) { num = 1.0; den = 1.0; }
+    double q = ddiv(num, den);
+    if (isq) q = ddiv(q, (double)C.max_cluster_length);
     float v = 0.0f;
-    if (l == 5) v = f32(ddiv((double)u.base_LP, (double)u.max_base_LP));
-    else if (l == 11) v = f32(ddiv(u.cost_def, u.max_cost));
-    else if (l == 12) v = f32(ddiv(u.cost_atk, u.max_cost));
+    if (isdiv) v = f32(q);
     else if (l == 13) v = f32(u.progress);
     else if (l >= 21 && l < 25) v = (u.cost_def >= C.t_price[l - 21][0]) ? 1.0f : 0.0f;
-    else if (l >= 41 && l < 45) v = f32(ddiv(ddiv(u.cost_def, C.e_cost[l - 41][0]), (double)C.max_cluster_length));
     S.chv[l] = v;
   }
-  d9_table(S, u.maxdist, l);
+  if ((need >> 9) & 1ull) d9_table(S, u.maxdist, l);  // wave-uniform
   wsync();
 }
 
@@ -246,61 +260,24 @@ __device__ __forceinline__ void write_obs(const Smem<NC>& S, const Ctx& x, OT* o
   }
 }
 
-// The class of every observation window, by the board's misalignment `mis` (units of
-// the 128-B line before the board) and window k, as a compile-time table read with one
-// scalar load per 8 windows (instead of the window's channel range, channel mask and
-// edge test in ~20 SALU per window): bits 0-1 the channel class (0 binary planes only,
-// 1 broadcast channels only, 2 enemy planes only, 3 mixed), bit 2 the window holds a
-// line shared with a neighbouring board.
-// UPL: units per 128-B line, 8 of float32 or 16 of float16 (ObsFmt) -- so many misalignments.
-template <int LT, int UPL = 8>
-struct ObsWinTab {
-  static constexpr int Q = LT * LT / 4, N4 = NCH * Q, K = (N4 + UPL - 1 + 63) / 64, W = (K + 7) / 8;
-  struct T { uint32_t w[UPL][W]; };
-  static constexpr uint32_t cls(int mis, int k) {
-    const int head = mis ? UPL - mis : 0, tail = ((N4 + mis) & ~(UPL - 1)) - mis;
-    const int ulo = 64 * k - mis, uhi = ulo + 63;
-    const int clo = (ulo < 0 ? 0 : ulo) / Q, chi = (uhi > N4 - 1 ? N4 - 1 : uhi) / Q;
-    uint64_t chm = 0;
-    for (int c = clo; c <= chi; ++c) chm |= 1ull << c;
-    chm &= kChAll;
-    const uint32_t c = (chm & ~kChBin) == 0 ? 0u : (chm & ~kChConst) == 0 ? 1u : (chm & ~kChEnemy) == 0 ? 2u : 3u;
-    return c | ((ulo < head || uhi >= tail) ? 4u : 0u);
-  }
-  static constexpr T make() {
-    T t{};
-    for (int m = 0; m < UPL; ++m)
-      for (int k = 0; k < K; ++k) t.w[m][k / 8] |= cls(m, k) << (4 * (k % 8));
-    return t;
-  }
-  static constexpr T tab = make();
-  // The dirty classes (OD_*, td_board.h) whose channels window k overlaps, 8 bits per
-  // window: a step that may skip (StepArgs::obs_skip) writes the window only if one of them
-  // is dirty.  (A window past the board's last unit, at a small `mis`, has none.)
-  static constexpr int WD = (K + 3) / 4;
-  struct D { uint32_t w[UPL][WD]; };
-  static constexpr uint32_t dirty(int mis, int k) {
-    const int ulo = 64 * k - mis, uhi = ulo + 63;
-    const int clo = (ulo < 0 ? 0 : ulo) / Q, chi = (uhi > N4 - 1 ? N4 - 1 : uhi) / Q;
-    uint32_t d = 0;
-    for (int c = clo; c <= chi; ++c) d |= obs_dirty_class(c);
-    return d;
-  }
-  static constexpr D make_d() {
-    D t{};
-    for (int m = 0; m < UPL; ++m)
-      for (int k = 0; k < K; ++k) t.w[m][k / 4] |= dirty(m, k) << (8 * (k % 4));
-    return t;
-  }
-  static constexpr D dtab = make_d();
-};
+// The channels a board's written windows read (see channel_scalars): every channel unless
+// the step kept its episode and may skip, then ObsWinTab::ntab by the board's misalignment
+// and its dirty classes (wave-uniform).  `out` as write_obs_lines takes it.
+template <int LT, class OT>
+__device__ __forceinline__ uint64_t obs_need(const OT* out, uint32_t dirty) {
+  typedef ObsFmt<OT> F;
+  if ((dirty & (OD_STATIC | OD_ALWAYS)) != OD_ALWAYS) return kChAll;
+  const int mis = (int)((reinterpret_cast<uintptr_t>(out) / F::UB) & (F::UPL - 1));
+  return ObsWinTab<LT, F::UPL>::ntab.w[mis][(__builtin_amdgcn_readfirstlane(dirty) >> 1) & 15u];
+}
 
 // The (45, L, L) float32 observation of one board for compile-time L, into a
 // 16-B-aligned buffer: the 128-B-aligned 1-KB windows of write_obs (store k covers
 // stream units [A + 64k, A + 64k + 64), A = the board's first unit rounded down to a
 // line), software-pipelined.  For G windows at a time every lane first issues its
-// two LDS reads -- the 16-B packed cell quad and one word that is the broadcast value
-// (chv) or the enemy group quad (grp) -- then the windows are computed and stored.
+// LDS reads -- the 16-B packed cell quad (at 10x10 not in a window of broadcast channels alone) and
+// one word that is the broadcast value (chv) or the enemy group quad (grp) -- then the
+// windows are computed and stored.
 // The window's channel mix is wave-uniform (SALU): a window of one class takes a
 // short path, the per-cell tables (channel 9, enemy stats) are read only where the
 // window holds such channels.  Stores are buffer stores whose lanes outside the board
@@ -367,6 +344,15 @@ __device__ __forceinline__ void write_obs_lines(const Smem<NC>& S, int lane, OT*
         if (wclean(k)) continue;
         const int i = unit(i0 + 64 * k, wc);
         const int ch = DivQ::div(i), q = i - ch * Q;
+        // 10x10: a window of broadcast channels alone reads the channel's value and no cell
+        // quad (-50 VALU, -169 SALU per wave of the retained step; at 20x20 and 30x30, whose
+        // window loop stays rolled, the same skip measured 0.9 and 1.5 % slower)
+        if constexpr (LT == 10) {
+          if ((wc & 3u) == 1) {
+            W[j] = *reinterpret_cast<const uint32_t*>(sb + o_chv + 4 * ch);
+            continue;
+          }
+        }
         A[j] = *reinterpret_cast<const uint4*>(sb + o_cell + 16 * q);
         if ((wc & 3u) == 1) {  // broadcast channels only: the channel's value
           W[j] = *reinterpret_cast<const uint32_t*>(sb + o_chv + 4 * ch);

@@ -186,8 +186,12 @@ __device__ __forceinline__ void skip_board(Smem<NC>& S, uint32_t* raw, const Ctx
   }
   if (refilled && x.lane < HOT_CACHE) sst(&hot[4 + x.lane], R.cache);
   const uint32_t dirty = obs_dirty(S, u, C, a.obs_skip != 0, was_reset);
+  uint64_t need = kChAll;  // the channels the written windows read (step_board)
+  if constexpr (LT != 0) {
+    if ((reinterpret_cast<uintptr_t>(a.obs) & (ObsFmt<OT>::UB - 1)) == 0) need = obs_need<LT, OT>(obs, dirty);
+  }
   enemy_stats(S, u, x);
-  channel_scalars(S, u, x);
+  channel_scalars(S, u, x, need);
   if (was_reset) {  // the new episode's layout
     store_cells(S, u, x, a, b);
     pack_obs_cells(S, x);
