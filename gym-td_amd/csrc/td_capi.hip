@@ -105,6 +105,7 @@ struct td_handle {
   std::string kernel_name;    // td_step_kernel_name
   std::string sel_kernel_name;  // td_step_boards_kernel_name
   std::string list_kernel_name;  // td_step_boards_dev_kernel_name
+  std::string mask_list_kernel_name;  // td_action_mask_boards_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -1127,32 +1128,88 @@ void td_mask_io_init(td_mask_io* io) {
   io->abi = TD_ABI_VERSION;
 }
 
-int td_action_mask(td_handle* h, const td_mask_io* io, void* stream) {
-  if (!io) return fail("td_action_mask: NULL io");
+namespace {
+
+// What td_action_mask and its list forms check of their io, in this order, and the kernel
+// arguments they make of it.  fn: the caller's name, for the message.
+int check_mask_io(const char* fn, const td_handle* h, const td_mask_io* io, MaskArgs* out) {
+  if (!io) return fail("%s: NULL io", fn);
   // the two header words first, as td_step
   if (io->size != (uint32_t)sizeof(td_mask_io) || io->abi != (uint32_t)TD_ABI_VERSION)
-    return fail("td_action_mask: td_mask_io has size %u / abi %u, this library expects size %u / abi %d "
-                "(call td_mask_io_init)", io->size, io->abi, (unsigned)sizeof(td_mask_io), TD_ABI_VERSION);
-  if (!h) return fail("td_action_mask: NULL handle");
-  if (!io->def_mask && !io->def_code && !io->atk_mask) return fail("td_action_mask: no output wanted (all three are NULL)");
+    return fail("%s: td_mask_io has size %u / abi %u, this library expects size %u / abi %d "
+                "(call td_mask_io_init)", fn, io->size, io->abi, (unsigned)sizeof(td_mask_io), TD_ABI_VERSION);
+  if (!h) return fail("%s: NULL handle", fn);
+  if (!io->def_mask && !io->def_code && !io->atk_mask) return fail("%s: no output wanted (all three are NULL)", fn);
   const bool def_out = io->def_mask || io->def_code;
-  if (def_out && h->mode == TD_MODE_ATK) return fail("td_action_mask: TD-atk has no defender side (def_mask / def_code)");
-  if (io->atk_mask && h->mode == TD_MODE_DEF) return fail("td_action_mask: TD-def has no attacker side (atk_mask)");
+  if (def_out && h->mode == TD_MODE_ATK) return fail("%s: TD-atk has no defender side (def_mask / def_code)", fn);
+  if (io->atk_mask && h->mode == TD_MODE_DEF) return fail("%s: TD-def has no attacker side (atk_mask)", fn);
   const size_t row = (size_t)6 * h->NC + (h->multi ? 0 : 1);
   size_t pitch = row;
   if (def_out && io->def_pitch != 0) {
-    if (h->multi) return fail("td_action_mask: def_pitch must be 0 with multi-action (rows are [6][L][L], contiguous)");
+    if (h->multi) return fail("%s: def_pitch must be 0 with multi-action (rows are [6][L][L], contiguous)", fn);
     if (io->def_pitch < row || io->def_pitch > kMaskMaxPitch)
-      return fail("td_action_mask: def_pitch %zu outside [%zu, %zu] (6 L^2 + 1 bytes per row at L = %d)", io->def_pitch, row,
+      return fail("%s: def_pitch %zu outside [%zu, %zu] (6 L^2 + 1 bytes per row at L = %d)", fn, io->def_pitch, row,
                   kMaskMaxPitch, h->L);
     pitch = io->def_pitch;
   }
-  MaskArgs a;
+  MaskArgs& a = *out;
   a.B = h->B; a.L = h->L; a.multi = h->multi; a.xcd_map = h->xcd_map;
   a.hdr = h->d_hdr; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.cfg = h->d_cfg + h->epoch;
   a.def_mask = io->def_mask; a.def_code = io->def_code; a.atk_mask = io->atk_mask; a.def_pitch = pitch;
+  return 0;
+}
+
+}  // namespace
+
+int td_action_mask(td_handle* h, const td_mask_io* io, void* stream) {
+  MaskArgs a;
+  if (check_mask_io("td_action_mask", h, io, &a)) return -1;
   HIP_OK(launch_mask(a, (hipStream_t)stream));
   return 0;
+}
+
+// td_action_mask for the boards named: the rows of every other board keep their bytes
+// (td_mask_list.hip).  Everything is checked here, before anything is enqueued; the ids reach
+// the kernel through the pinned id slots and d_pairs (upload_ids), as td_step_boards'.  The call
+// only reads state: it is no launch for the refill cadence or the ring guard, takes no timing
+// pair and leaves the observation ledger alone.
+int td_action_mask_boards(td_handle* h, const td_mask_io* io, const int32_t* boards, int n, void* stream) {
+  MaskArgs a;
+  if (check_mask_io("td_action_mask_boards", h, io, &a)) return -1;
+  char msg[200];
+  if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("td_action_mask_boards: %s", msg);
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (upload_ids(h, boards, nullptr, n, s)) return -1;
+  HIP_OK(launch_mask_list(a, h->d_pairs, n, nullptr, nullptr, s));
+  return 0;
+}
+
+// The same for a list, its length and its verdict in device memory, under td_step_boards_dev's
+// contract: the host checks what it can see, the check kernel the contents, on the stream in
+// front of the mask kernel; a refused list writes no output byte.
+int td_action_mask_boards_dev(td_handle* h, const td_mask_io* io, const int32_t* boards_dev, int cap,
+                              const int32_t* count_dev, td_list_status* status_dev, void* stream) {
+  // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
+  if (io && io->size == (uint32_t)sizeof(td_mask_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
+    return fail("td_action_mask_boards_dev: cap = %d is negative", cap);
+  MaskArgs a;
+  if (check_mask_io("td_action_mask_boards_dev", h, io, &a)) return -1;
+  if (cap > h->B) return fail("td_action_mask_boards_dev: cap = %d outside [0, %d] (the handle's boards)", cap, h->B);
+  if (cap == 0) return 0;
+  if (!boards_dev) return fail("td_action_mask_boards_dev: boards_dev is NULL with cap = %d", cap);
+  hipStream_t s = (hipStream_t)stream;
+  if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
+  HIP_OK(launch_mask_list(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
+  return 0;
+}
+
+const char* td_action_mask_boards_kernel_name(td_handle* h) {
+  if (!h) return "";
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "td_mask_list_kernel<%d>", with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
+  h->mask_list_kernel_name = buf;
+  return h->mask_list_kernel_name.c_str();
 }
 
 int td_set_step_kernel(td_handle* h, int kind) {

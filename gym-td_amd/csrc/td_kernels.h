@@ -1,6 +1,7 @@
 // td_kernels.h -- interface between the C-ABI (td_capi.hip) and the kernel units: the kernels'
 // arguments, the row lookups of the step, frame-skip and partial-step units (launched through
-// td_step_launch.h) and the launch_* functions of td_reset.hip, td_mask.hip and td_copy.hip.
+// td_step_launch.h) and the launch_* functions of td_reset.hip, td_mask.hip, td_mask_list.hip and
+// td_copy.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -166,6 +167,19 @@ struct MaskArgs {
 };
 constexpr size_t kMaskMaxPitch = 1u << 16;
 hipError_t launch_mask(const MaskArgs& a, hipStream_t s);
+// The same masks for the boards a list names, every other row left as it is
+// (td_action_mask_boards[_dev]; td_mask_list.hip): boards ids[0 .. cap) of device memory where
+// verdict == nullptr (the ids validated by the caller); else boards ids[0 .. *count) (count ==
+// nullptr: cap), unless verdict->code says the check kernel launched in front refused the list:
+// then nothing is read of any board and nothing is written.  One wave per entry of cap >= 1,
+// kMaskListWaves entries per workgroup (TD_MASK_LIST_WAVES: a build-time measurement knob).
+#ifndef TD_MASK_LIST_WAVES
+#define TD_MASK_LIST_WAVES 4
+#endif
+constexpr int kMaskListWaves = TD_MASK_LIST_WAVES;
+static_assert(kMaskListWaves >= 1 && kMaskListWaves <= 8, "waves of one workgroup (their LDS rows: 64 KB)");
+hipError_t launch_mask_list(const MaskArgs& a, const int32_t* ids, int cap, const int32_t* count,
+                            const td_list_status* verdict, hipStream_t s);
 
 // Staged layouts per board: sixteen episodes of slack for the side refills, and the
 // ring guard (td_refill_kernel) needs to run only every NSLOT - 1 steps.  (NSLOT = 4 with

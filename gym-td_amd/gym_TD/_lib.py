@@ -111,6 +111,10 @@ def _load():
         "td_list_errors": (ctypes.c_int, [c_vp, ctypes.POINTER(TdListStatus), ctypes.c_int]),
         "td_mask_io_init": (None, [ctypes.POINTER(TdMaskIO)]),
         "td_action_mask": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp]),
+        "td_action_mask_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp, ctypes.c_int, c_vp]),
+        "td_action_mask_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp, ctypes.c_int, c_vp, c_vp,
+                                                     c_vp]),
+        "td_action_mask_boards_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
         "td_layout_from_roads": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_u32p]),
         "td_layout_generate": (ctypes.c_int, [c_u32p, ctypes.c_int, ctypes.c_int, c_u32p]),

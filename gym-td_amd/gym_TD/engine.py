@@ -172,6 +172,9 @@ class TDEngine(object):
                  np_seeds=None, py_seeds=None, autoreset=True, info=True, cfg=None, hp=None, host_io=False,
                  random_agent=True, step_kernel="auto", obs_dtype=torch.float32, retain_obs=True, frame_skip=1):
         frame_skip = _check_frame_skip(frame_skip)  # (before td_create: no device is touched)
+        # state serial: advanced by every call that can change a board or the config (_changed);
+        # _mask_at: the serial at which the mask / code buffers were last written whole
+        self._state_serial, self._mask_at, self._mask_pending = 0, {}, None
         if obs_dtype not in OBS_FORMATS:  # (before td_create: no device is touched)
             raise ValueError("obs_dtype must be torch.float32 or torch.float16, not %r" % (obs_dtype,))
         if not isinstance(retain_obs, (bool, np.bool_)):
@@ -288,6 +291,7 @@ class TDEngine(object):
         enemies and towers keep the values they were created / upgraded with, and each
         board the max_cost / base_LP of its last reset (TDElements.py:4-69, TDBoard.py:66-72)."""
         self._cfg_c = P.to_c(cfg or P.config, hp)
+        self._changed()
         _lib.check(_lib.lib.td_set_config(self._h, self._cfg_c))
         self._cfg_hist[_lib.lib.td_config_epoch(self._h)] = copy.deepcopy(cfg or P.config)
 
@@ -342,6 +346,7 @@ class TDEngine(object):
         if mask is not None:
             m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(self.B))
         torch.cuda.synchronize(self.device)
+        self._changed()
         rc = _lib.lib.td_reset(self._h, _lib.ptr(m, _lib.ctypes.c_uint8) if m is not None else None,
                                self.obs.data_ptr(), self._stream())
         _lib.check(rc)
@@ -372,6 +377,7 @@ class TDEngine(object):
         recs = _u32(recs).reshape(-1, self.lw)
         ids = np.ascontiguousarray(boards, dtype=np.int32)
         torch.cuda.synchronize(self.device)
+        self._changed()
         _lib.check(_lib.lib.td_reset_layouts(self._h, _lib.ptr(recs, _lib.ctypes.c_uint32),
                                              _lib.ptr(ids, _lib.ctypes.c_int32), len(ids), self.obs.data_ptr(),
                                              self._stream()))
@@ -433,11 +439,14 @@ class TDEngine(object):
     def _call_step(self, io, ids, dev):
         if dev is not None:
             b, c, st = dev
+            self._changed(("dev", b, c))
             return _lib.lib.td_step_boards_dev(self._h, io, b.data_ptr(), int(b.numel()),
                                                c.data_ptr() if c is not None else None,
                                                st.data_ptr() if st is not None else None, self._stream())
         if ids is None:
+            self._changed()
             return _lib.lib.td_step(self._h, io, self._stream())
+        self._changed(("host", ids.copy()))
         return _lib.lib.td_step_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream())
 
     def _launch_step(self, def_act, atk_act, ids=None, dev=None):
@@ -499,6 +508,7 @@ class TDEngine(object):
         s, d = _board_ids(src), _board_ids(dst)
         if s.shape != d.shape:
             raise ValueError("src and dst must name equally many boards, got %d and %d" % (s.size, d.size))
+        self._changed(("host", d.copy()))
         _lib.check(_lib.lib.td_copy_boards(self._h, s.ctypes.data, d.ctypes.data, int(s.size),
                                            self.obs.data_ptr() if write_obs else None, self._stream()))
         return self.obs
@@ -520,6 +530,7 @@ class TDEngine(object):
             raise ValueError("src and dst must name equally many boards, got %d and %d" % (s.numel(), d.numel()))
         c = _dev_words(count, 1, self.device, "count")
         st = _dev_words(status, 4, self.device, "status")
+        self._changed(("dev", d, c))
         _lib.check(_lib.lib.td_copy_boards_dev(self._h, s.data_ptr(), d.data_ptr(), int(s.numel()),
                                                c.data_ptr() if c is not None else None,
                                                self.obs.data_ptr() if write_obs else None,
@@ -530,7 +541,7 @@ class TDEngine(object):
         return self.obs
 
     def list_errors(self, clear=True):
-        """Device-list calls (``step_boards_dev``, ``copy_boards_dev``) whose list the device
+        """Device-list calls (``step_boards_dev``, ``copy_boards_dev``, ``action_mask_boards_dev``) whose list the device
         refused since the last clear (td_list_errors; waits for the device): ``(n_refused,
         first)``, ``first`` None or a dict with ``code`` (1 count, 2 range, 3 twice, 4 overlap),
         ``call`` (the call's serial), ``entry`` and ``board``."""
@@ -543,18 +554,8 @@ class TDEngine(object):
         """The kernel ``step_boards_dev`` launches behind its check (td_step_boards_dev_kernel_name)."""
         return _lib.lib.td_step_boards_dev_kernel_name(self._h).decode()
 
-    def action_mask(self, code=False):
-        """Legal-action masks of every board's present state (td_action_mask): what the next
-        step() would execute if the action were the only thing asked of that side.
-
-        Returns a dict of uint8 device tensors, by mode: ``"def"`` (B, 6 L^2 + 1), the
-        no-op last -- or (B, 6, L, L) with multi-action, each flag on its own --,
-        ``"def_code"`` (with ``code``: the fail code each operation would return, the
-        cool-down aside) and ``"atk"`` (B, 3, 5), type 4 = none.  One kernel on torch's
-        current stream, which must be the stream of step().  The tensors are the engine's
-        own buffers (allocated on first use, overwritten by the next call); the discrete
-        defender rows are padded to a multiple of 16 bytes, the returned tensor is the
-        view without the padding."""
+    def _mask_prepare(self, code):
+        """The engine's mask buffers (allocated on first use) as a td_mask_io."""
         B, L = self.B, self.L
         io = getattr(self, "_mask_io", None)
         if io is None:
@@ -576,13 +577,109 @@ class TDEngine(object):
         if code and self.mode != "atk" and "def_code" not in self._mask_buf:
             self._mask_buf["def_code"] = torch.zeros(self._mask_shape, dtype=torch.uint8, device=self.device)
         io.def_code = self._mask_buf["def_code"].data_ptr() if code and self.mode != "atk" else None
-        _lib.check(_lib.lib.td_action_mask(self._h, io, self._stream()))
-        A = 6 * L * L + 1
+        return io
+
+    def _mask_views(self, code):
+        A = 6 * self.L * self.L + 1
         out = {}
         for k, t in self._mask_buf.items():
             if k == "def_code" and not code:
                 continue
             out[k] = t[:, :A] if k != "atk" and not self.multi else t
+        return out
+
+    def action_mask(self, code=False):
+        """Legal-action masks of every board's present state (td_action_mask): what the next
+        step() would execute if the action were the only thing asked of that side.
+
+        Returns a dict of uint8 device tensors, by mode: ``"def"`` (B, 6 L^2 + 1), the
+        no-op last -- or (B, 6, L, L) with multi-action, each flag on its own --,
+        ``"def_code"`` (with ``code``: the fail code each operation would return, the
+        cool-down aside) and ``"atk"`` (B, 3, 5), type 4 = none.  One kernel on torch's
+        current stream, which must be the stream of step().  The tensors are the engine's
+        own buffers (allocated on first use, overwritten by the next call); the discrete
+        defender rows are padded to a multiple of 16 bytes, the returned tensor is the
+        view without the padding."""
+        io = self._mask_prepare(code)
+        _lib.check(_lib.lib.td_action_mask(self._h, io, self._stream()))
+        # every row of the buffers written describes the present state (refresh_action_mask)
+        self._mask_at["mask"] = self._state_serial
+        if code and self.mode != "atk":
+            self._mask_at["code"] = self._state_serial
+        return self._mask_views(code)
+
+    def action_mask_boards(self, boards, code=False):
+        """``action_mask`` for the boards named in ``boards`` only (td_action_mask_boards): with
+        ``copy_boards`` and ``step_boards`` the third call of a search iteration -- fork the
+        leaves, step the leaves, mask the leaves -- at the cost of the leaves.
+
+        ``boards``: board ids under ``step_boards``' rules (int sequence, numpy array or tensor;
+        a GPU tensor is brought to the host first), any order, none twice.  Writes into the
+        engine's own mask buffers, the ones ``action_mask()`` returns (allocated on first use),
+        and returns the same dict of full tensors: only the named rows are fresh, every other
+        row keeps the bytes it had, whatever state they describe.  One kernel on torch's
+        current stream, which must be the stream of step(); nothing is synchronised, no board
+        changes.  An empty list is a no-op.  TDError, nothing written: an id out of range or
+        named twice.  ``frame_skip`` > 1 and random_agent=False are fine here.
+        Ids that are on the device already: ``action_mask_boards_dev``."""
+        ids = _board_ids(boards)
+        io = self._mask_prepare(code)
+        _lib.check(_lib.lib.td_action_mask_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
+        return self._mask_views(code)
+
+    def action_mask_boards_dev(self, boards, count=None, status=None, code=False):
+        """``action_mask_boards`` for ids that are on the device (td_action_mask_boards_dev):
+        nothing is copied to the host and nothing is waited for; the list is validated by a
+        kernel on the stream, in front of the mask's.
+
+        ``boards``, ``count`` and ``status`` as in ``step_boards_dev`` (a CPU tensor, list or
+        numpy array raises ValueError: that is ``action_mask_boards``).  A list the device
+        refuses (a count outside [0, cap], an id out of range, a board named twice) writes no
+        byte; ``list_errors()`` tells afterwards.  Returns the engine's full mask tensors:
+        only the named rows are fresh.  The tensors stay alive until the next call."""
+        ids = _dev_ids(boards, self.device, "action_mask_boards")
+        c = _dev_words(count, 1, self.device, "count")
+        st = _dev_words(status, 4, self.device, "status")
+        io = self._mask_prepare(code)
+        _lib.check(_lib.lib.td_action_mask_boards_dev(self._h, io, ids.data_ptr(), int(ids.numel()),
+                                                      c.data_ptr() if c is not None else None,
+                                                      st.data_ptr() if st is not None else None, self._stream()))
+        self._keep_mask_list = (ids, c, st)  # alive until the next call's kernels are behind them on the stream
+        return self._mask_views(code)
+
+    def action_mask_boards_kernel_name(self):
+        """The kernel ``action_mask_boards`` and ``action_mask_boards_dev`` launch
+        (td_action_mask_boards_kernel_name), e.g. 'td_mask_list_kernel<10>'."""
+        return _lib.lib.td_action_mask_boards_kernel_name(self._h).decode()
+
+    def _changed(self, rows=None):
+        """Called in front of every call that can change a board or the config: the state
+        serial advances.  rows: the boards the call can change, ``("host", int32 array)`` or
+        ``("dev", ids, count)``; None = any board, or the config."""
+        self._mask_pending = (self._state_serial, rows) if rows is not None else None
+        self._state_serial += 1
+
+    def refresh_action_mask(self, code=False):
+        """``action_mask(code)`` -- the same tensors with the same bytes -- at the cost of the
+        rows that changed, where the engine knows which: the mask buffers were written whole
+        for the state just before the engine's most recent state-changing call, and that call
+        was a list step or a board copy.  Then only its boards (the copy's destinations) are
+        computed again, by ``action_mask_boards`` or ``action_mask_boards_dev`` on the call's
+        own list.  In every other case (the first call, a ``step()``, a reset, a config change, a
+        state import, the opponent, or two changes since the last mask) this is ``action_mask``.
+        A device list must still hold what the call read."""
+        p = self._mask_pending
+        keys = ("mask", "code") if code and self.mode != "atk" else ("mask",)
+        if p is None or p[0] != self._state_serial - 1 or any(self._mask_at.get(k) != p[0] for k in keys):
+            return self.action_mask(code)
+        rows = p[1]
+        if rows[0] == "host":
+            out = self.action_mask_boards(rows[1], code=code)
+        else:
+            out = self.action_mask_boards_dev(rows[1], count=rows[2], code=code)
+        self._mask_pending = None
+        for k in keys:
+            self._mask_at[k] = self._state_serial
         return out
 
     # ----------------------------------------------------------------- state
@@ -603,6 +700,7 @@ class TDEngine(object):
         count = len(st["hdr"])
         buf = _encode_state(st, count, self.L)
         torch.cuda.synchronize(self.device)
+        self._changed()
         _lib.check(_lib.lib.td_import_state(self._h, b0, count, buf.ctypes.data))
 
     def episode_stats(self, clear=False):
@@ -627,6 +725,7 @@ class TDEngine(object):
         m = None
         if mask is not None:
             m = np.ascontiguousarray(np.asarray(mask, dtype=np.uint8).reshape(self.B))
+        self._changed()
         _lib.check(_lib.lib.td_opponent(self._h, {"enemy": 0, "tower": 1}[side], int(level),
                                         _lib.ptr(m, _lib.ctypes.c_uint8) if m is not None else None, self._stream()))
 

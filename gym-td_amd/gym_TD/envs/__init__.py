@@ -323,7 +323,7 @@ class TDVecEnv(object):
     101-103): the built-in opponents draw from each board's layout stream, and each
     auto-reset draws the next layout right after the step that ended the episode,
     as AsyncVectorEnv's reset() would.  ``action_mask=True``: every step() and reset() is
-    followed by the mask kernel, and ``infos['action_mask']`` (the side that acts; the
+    followed by the mask kernel (the search calls by its list form, for the rows that changed), and ``infos['action_mask']`` (the side that acts; the
     defender's in TD-2p) and ``infos['action_mask_attacker']`` (TD-atk, TD-2p) hold the legal actions
     of the state the step left (TDEngine.action_mask); after reset(), ``action_masks()``.
     ``obs_dtype=torch.float16``: the observation as float16 (TDEngine's ``obs_dtype``).
@@ -368,11 +368,13 @@ class TDVecEnv(object):
         """Make envs ``dst[i]`` exact copies of envs ``src[i]`` between two steps, on the device
         (TDEngine.copy_boards): search forks -- what ``copy.deepcopy(env)`` is to a reference
         env.  Returns the observation tensor, the copies' rows written; with
-        ``action_mask=True`` the masks are computed again for the new states.  The last
+        ``action_mask=True`` the masks are computed again for the new states -- for ``dst``'s
+        rows alone where the engine knows every other row is current
+        (TDEngine.refresh_action_mask), the same bytes either way.  The last
         step's reward, done and infos keep ``dst``'s old rows until the next step."""
         obs = self.engine.copy_boards(src, dst)
-        if self.with_action_mask:
-            self._masks = self.engine.action_mask()
+        if self.with_action_mask:  # only dst's rows, where the engine knows the others are current
+            self._masks = self.engine.refresh_action_mask()
         return obs
 
     def step(self, actions):
@@ -382,27 +384,32 @@ class TDVecEnv(object):
         """step() for the envs named in ``boards`` only (TDEngine.step_boards): ``actions`` as
         for step(), full-batch, read at the named rows; every other env keeps its state and
         its rows.  Returns step()'s tuple, the full tensors with the named rows fresh; with
-        ``action_mask=True`` the masks are computed again.  With fork() the loop of a search:
+        ``action_mask=True`` the masks are computed again (the named boards' rows alone where
+        every other row is known to be current: the full masks either way).  With fork() the loop of a search:
         fork the leaves, step the leaves, read their rows and masks."""
-        return self._step(actions, lambda **kw: self.engine.step_boards(boards, **kw))
+        return self._step(actions, lambda **kw: self.engine.step_boards(boards, **kw), partial=True)
 
     def fork_dev(self, src, dst, count=None, status=None):
         """fork() for env ids that are on the device (TDEngine.copy_boards_dev): integer device
         tensors, an optional one-element int32 ``count`` tensor and a 4-element int32
         ``status`` tensor for the verdict; nothing is copied to the host or waited for.  A list
-        the device refuses changes nothing (``engine.list_errors()``)."""
+        the device refuses changes nothing (``engine.list_errors()``).  With ``action_mask=True``
+        the masks follow as in fork(), by the same device list (TDEngine.action_mask_boards_dev:
+        a refused list is refused, and counted, there too)."""
         obs = self.engine.copy_boards_dev(src, dst, count=count, status=status)
-        if self.with_action_mask:
-            self._masks = self.engine.action_mask()
+        if self.with_action_mask:  # only dst's rows, where the engine knows the others are current
+            self._masks = self.engine.refresh_action_mask()
         return obs
 
     def step_boards_dev(self, boards, actions, count=None, status=None):
         """step_boards() for env ids that are on the device (TDEngine.step_boards_dev): with
         fork_dev() a search iteration without a host round trip.  ``count`` / ``status`` as in
-        fork_dev(); with ``action_mask=True`` the masks are computed again."""
-        return self._step(actions, lambda **kw: self.engine.step_boards_dev(boards, count=count, status=status, **kw))
+        fork_dev(); with ``action_mask=True`` the masks are computed again, as in step_boards(),
+        by the same device list."""
+        return self._step(actions, lambda **kw: self.engine.step_boards_dev(boards, count=count, status=status, **kw),
+                          partial=True)
 
-    def _step(self, actions, run):
+    def _step(self, actions, run, partial=False):
         if self.mode == "def":
             obs, rew, done = run(def_act=actions)
         elif self.mode == "atk":
@@ -425,7 +432,8 @@ class TDVecEnv(object):
                 infos["RealActionAttacker"] = e.real_atk
                 infos["FailCodeAttacker"] = e.fail_atk
         if self.with_action_mask:
-            m = self._masks = e.action_mask()
+            # a list step: only the list's rows, where the engine knows the others are current
+            m = self._masks = e.refresh_action_mask() if partial else e.action_mask()
             infos["action_mask"] = m["atk" if self.mode == "atk" else "def"]
             if self.mode != "def":
                 infos["action_mask_attacker"] = m["atk"]

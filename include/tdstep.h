@@ -469,7 +469,7 @@ int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards
  * comment above td_step_boards_dev says.  Asynchronous on `stream`, the step's stream. */
 int td_copy_boards_dev(td_handle* h, const int32_t* src_dev, const int32_t* dst_dev, int cap,
                        const int32_t* count_dev, float* obs, td_list_status* status_dev, void* stream);
-/* How many device-list calls (td_step_boards_dev, td_copy_boards_dev) the device refused since
+/* How many device-list calls (td_step_boards_dev, td_copy_boards_dev, td_action_mask_boards_dev) the device refused since
  * the last clear, and in *first (may be NULL) the record of the first of them; with no refusal
  * *first is all zero (code = TD_LIST_OK).  clear != 0 zeroes the count and the record.  Waits
  * for the device's work first -- synchronous, the pattern of td_guard_timeouts: a search loop
@@ -518,6 +518,42 @@ typedef struct td_mask_io {
 /* Zero *io and set its size / abi words. */
 void td_mask_io_init(td_mask_io* io);
 int td_action_mask(td_handle* h, const td_mask_io* io, void* stream);
+
+/* td_action_mask for the boards a list names: the third call of a search iteration, beside
+ * td_copy_boards (fork the leaves) and td_step_boards (step the leaves), in both of their
+ * flavours.  io is td_action_mask's, unchanged: the outputs keep their full-batch shape and are
+ * indexed by board id -- def_mask, def_code, atk_mask, def_pitch, the multi-action [B][6][L][L]
+ * form, any alignment.  Row b of every wanted output is written for every named board b, byte
+ * for byte what td_action_mask writes there; no byte of an unnamed row changes, the 16-B pieces
+ * and 128-B lines it shares with a named neighbour included (a pitch that is no multiple of 16,
+ * the 15-B attacker rows).
+ * The calls write nothing but these outputs: no board, RNG stream or flag changes, the
+ * retained-observation ledger is not touched, they are no launch for the refill cadence or the
+ * ring guard, and they take no td_kernel_timing pair (as td_action_mask takes none).  One wave
+ * per list entry, several entries per workgroup (td_action_mask_boards_kernel_name).
+ * Asynchronous on `stream`, which must be the step's stream.
+ * td_action_mask_boards -- a host list, under td_step_boards' rules: order free, the array is
+ *   the caller's again on return, n == 0 returns 0 and launches nothing.  Refused (< 0,
+ *   td_last_error with the call's name; on the host, before anything is enqueued, so no output
+ *   byte changes), in this order: a NULL io, a bad size / abi word, a NULL handle, no output
+ *   wanted, an output for a side the mode lacks, a bad pitch (all as td_action_mask); n < 0 or
+ *   n > the handle's boards; NULL boards with n > 0; an id outside [0, boards); an id named
+ *   twice.  Unlike the step, td_frame_skip() > 1 and random_agent = 0 with auto-reset are no
+ *   reason to refuse: the kernel only reads state.
+ * td_action_mask_boards_dev -- a device list, under td_step_boards_dev's contract word for word
+ *   where it applies: cap and count_dev, the lifetime of the id memory, status_dev, and the
+ *   split of the refusals.  On the host: td_action_mask's refusals with this call's name, cap
+ *   < 0 (with the io words, before the handle), cap > the handle's boards, NULL boards_dev with
+ *   cap > 0; cap == 0 returns 0 and launches nothing.  On the device (td_list_check_kernel in
+ *   front, the call takes the next serial of the handle's device-list calls):
+ *   TD_LIST_BAD_COUNT, TD_LIST_RANGE, TD_LIST_TWICE -- then no output byte is written, the call
+ *   returned 0, and td_list_errors counts the refusal. */
+int td_action_mask_boards(td_handle* h, const td_mask_io* io, const int32_t* boards, int n, void* stream);
+int td_action_mask_boards_dev(td_handle* h, const td_mask_io* io, const int32_t* boards_dev, int cap,
+                              const int32_t* count_dev, td_list_status* status_dev, void* stream);
+/* The kernel both calls launch, as rocprofv3 shows it: "td_mask_list_kernel<10>" (L, or 0 for a
+ * generic side).  The string is the handle's, valid until the next call. */
+const char* td_action_mask_boards_kernel_name(td_handle* h);
 
 /* Which step kernel td_step launches (one wave per board in all three; they differ in
  * occupancy and load schedule, not in results):
