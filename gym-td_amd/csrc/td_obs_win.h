@@ -38,7 +38,7 @@ constexpr uint64_t kChConst = kChAll & ~(kChBin | kChD9 | kChEnemy);
 // its last write left it.  STATIC: the layout (roads, end, starts, distance, channel 10),
 // new only with a new episode; LP: channel 5 (a leak); TOWER: buildable, tower level / type
 // (the tower list changed); COST: channels 21-24 (cost_def crossed a tower cost); ENEMY:
-// the enemy planes (an enemy before or after the step); ALWAYS: costs, progress, channels
+// the enemy planes (the step touched an enemy: U::en_touch, obs_dirty); ALWAYS: costs, progress, channels
 // 41-44.
 enum : uint32_t { OD_STATIC = 1u, OD_LP = 2u, OD_TOWER = 4u, OD_COST = 8u, OD_ENEMY = 16u, OD_ALWAYS = 32u, OD_ALL = 63u };
 __host__ __device__ constexpr uint32_t obs_dirty_class(int ch) {

@@ -56,7 +56,7 @@ __device__ __forceinline__ void step_board(Smem<NC>& S, const Ctx& x, const Step
   // what the dirty classes compare with after the step (obs_dirty), kept in LDS: the small
   // kernels have no SGPR to carry it across the step
   if (x.lane == 0) {
-    S.before = cost_bits(u.cost_def, C) | (u.n > 0 ? 16u : 0u);
+    S.before = cost_bits(u.cost_def, C);
     S.before_lp = u.base_LP;
   }
   const int64_t act_in =(int64_t)(((uint64_t)lane_word(P.w, PF_ACT + 1) << 32) | lane_word(P.w, PF_ACT));

@@ -464,12 +464,20 @@ __device__ __forceinline__ uint32_t cost_bits(double cost_def, const TdDevCfg& C
 // board as loaded (Smem::before, before_lp).  Every class unless the step may skip
 // (StepArgs::obs_skip) and the board kept its episode: a new episode has a new layout.
 // tw_dirty: the tower list changed (it decides the tower-word stores too).
+// The enemy planes hold, per (type, cell), the minimum, maximum and mean (summed in list
+// order) of LP / max LP and count / max_cluster_length.  They are dirty only when the step
+// touched one of those (U::en_touch): an enemy was summoned (summon_cluster), the stable sort
+// moved one, a tower's shot landed, or an enemy entered a new cell (board_step) -- a kill
+// implies a shot, a leak a move.  The slow-down counter, the margin and the cool-downs are not
+// in the observation; max_cluster_length and an enemy's captured max LP change only with the
+// config, and a config change forces a launch that may not skip (td_obs_ledger.h).  A board
+// whose enemy stands in its cell unshot keeps its 16 planes as they are.
 template <int NC>
 __device__ __forceinline__ uint32_t obs_dirty(const Smem<NC>& S, const U& u, const TdDevCfg& C, bool skip, bool was_reset) {
   if (!skip || was_reset) return OD_ALL;
   const uint32_t bf = S.before;
   return OD_ALWAYS | (u.tw_dirty ? OD_TOWER : 0u) | (u.base_LP != S.before_lp ? OD_LP : 0u) |
-         (cost_bits(u.cost_def, C) != (bf & 15u) ? OD_COST : 0u) | (((bf & 16u) != 0u || u.n > 0) ? OD_ENEMY : 0u);
+         (cost_bits(u.cost_def, C) != (bf & 15u) ? OD_COST : 0u) | (u.en_touch ? OD_ENEMY : 0u);
 }
 constexpr uint32_t kEarlyGo = 0x80000000u;  // Smem::early_go: the second wave's early pass may run (| its dirty classes)
 

@@ -288,6 +288,7 @@ __device__ __forceinline__ int summon_cluster(Smem<NC>& S, U& u, const Ctx& x, u
           S.eInf[u.n] = en_pack(st, t, lv, 0, x.ep);
         }
         u.n += 1;
+        u.en_touch = true;  // a new enemy: its group's planes change
         summoned = true;
       }
     }
@@ -345,18 +346,24 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
         if (kj < key[s] || (kj == key[s] && j < i)) rank[s] += 1;
       }
     }
-    wsync();
+    // The sort is the identity on almost every board (enemies enter in order and keep it): the
+    // lanes hold the sorted list already, no scatter through LDS.  A sort that moves an enemy
+    // changes the order a group's LP ratios are summed in (enemy_stats).
+    if (ballot((val[0] && rank[0] != lane) || (val[1] && rank[1] != lane + 64)) != 0ull) {
+      u.en_touch = true;
+      wsync();
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
-      if (val[s]) { S.eLP[rank[s]] = lp[s]; S.eMg[rank[s]] = mg[s]; S.eInf[rank[s]] = inf[s]; }
-    wsync();
-    // lane owns sorted enemies lane and lane + 64
+      for (int s = 0; s < 2; ++s)
+        if (val[s]) { S.eLP[rank[s]] = lp[s]; S.eMg[rank[s]] = mg[s]; S.eInf[rank[s]] = inf[s]; }
+      wsync();
+      // lane owns sorted enemies lane and lane + 64
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      int i = lane + 64 * s;
-      lp[s] = val[s] ? S.eLP[i] : 0.0;
-      mg[s] = val[s] ? S.eMg[i] : 0.0;
-      inf[s] = val[s] ? S.eInf[i] : 0u;
+      for (int s = 0; s < 2; ++s) {
+        int i = lane + 64 * s;
+        lp[s] = val[s] ? S.eLP[i] : 0.0;
+        mg[s] = val[s] ? S.eMg[i] : 0.0;
+        inf[s] = val[s] ? S.eInf[i] : 0u;
+      }
     }
   }
 
@@ -412,7 +419,9 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
       if (tries && cd < 0.0) cd = 0.0;                       // :311-312
       if (tk) tcd = cd;
       const uint32_t slow = (uint32_t)C.frozen_time << 16;   // config.frozen_time, read live (:126)
-      for (uint64_t fm = ballot(tgt >= 0); fm; fm &= fm - 1) {  // the towers that fired, in order
+      uint64_t fm = ballot(tgt >= 0);
+      if (fm) u.en_touch = true;  // a shot lands: LP, a kill or a slow-down with its LP loss
+      for (; fm; fm &= fm - 1) {  // the towers that fired, in order
         const int k = ctz64(fm);
         const int kt = (int)((rdl(tinf_l, k) >> 12) & 3u);
         const double atk = tp[4 * k + 2];
@@ -439,6 +448,7 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
         uint64_t m0 = ballot(in0), m1 = ballot(in1);
         if (m0 | m1) {
           const int tgt = m0 ? ctz64(m0) : 64 + ctz64(m1);
+          u.en_touch = true;  // a shot lands
           cd = dadd(cd, tp[4 * k + 1]);  // cd += intv
           const double atk = tp[4 * k + 2];
           if (tt <= 1) {  // TowerArrow / TowerMagic (TDElements.py:71-93)
@@ -485,6 +495,7 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
   // --- march (:319-344)
   bool alive[2] = {val[0] && !dead0, val[1] && !dead1};
   bool leak[2] = {false, false};
+  bool walked = false;  // the enemy entered a new cell (or leaked)
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
     if (!alive[s]) continue;
@@ -495,6 +506,7 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
     if (slow > 0) { mg[s] = dadd(mg[s], dmul(sp, C.frozen_ratio)); slow -= 1; }
     else mg[s] = dadd(mg[s], sp);
     while (mg[s] >= 1.0) {
+      walked = true;
       mg[s] = dsub(mg[s], 1.0);
       const int d = pk_dir(S.cell[cell]);
       // map[5] codes (TDBoard.py:319): 0:+c 1:-c 2:+r 3:-r
@@ -508,6 +520,7 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
   }
   // a bad move is rare and lane-local: fold the flag into the uniform copy
   if (ballot((u.flags & FLAG_BAD_MOVE) != 0)) u.flags |= FLAG_BAD_MOVE;
+  if (ballot(walked)) u.en_touch = true;
   const int nl = popc64(ballot(leak[0])) + popc64(ballot(leak[1]));
   for (int p = 0; p < nl; ++p) {                            // :336-343, in list order
     if (u.base_LP > 0) reward = dsub(reward, C.penalty_leak);

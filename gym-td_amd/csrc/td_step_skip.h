@@ -48,7 +48,7 @@ __device__ __forceinline__ void skip_board(Smem<NC>& S, uint32_t* raw, const Ctx
   load_board<NC, PF_LARGE, PF_LARGE>(S, u, x, a, b, P);
   // what the buffer holds: the board as loaded at the start of the macro step (obs_dirty)
   if (x.lane == 0) {
-    S.before = cost_bits(u.cost_def, C) | (u.n > 0 ? 16u : 0u);
+    S.before = cost_bits(u.cost_def, C);
     S.before_lp = u.base_LP;
   }
   const int64_t act_in = (int64_t)(((uint64_t)lane_word(P.w, PF_ACT + 1) << 32) | lane_word(P.w, PF_ACT));

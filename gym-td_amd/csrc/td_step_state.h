@@ -43,7 +43,7 @@ struct alignas(16) Smem {
   };
   uint32_t early_go;         // td_step_kernel_small2: the binary-plane windows may be written early (kEarlyGo | dirty classes)
   int32_t flags0;            // the board's flags as loaded (store_board: is the header's second half dirty?)
-  uint32_t before;           // the board as loaded, for the dirty classes: cost_bits (bits 0-3), an enemy (bit 4)
+  uint32_t before;           // the board as loaded, for the dirty classes: cost_bits (bits 0-3)
   int32_t before_lp;         // ... and its base_LP
   TdDevCfg cfg;           // constant block, staged once per board: per-lane table lookups hit LDS
 };
@@ -79,6 +79,7 @@ struct U {
   int max_base_LP;  // captured at reset (TDBoard.py:72)
   bool cells_dirty;  // map[6] changed (tower built / destroyed) or a new layout: write the cells back
   bool tw_dirty;     // the tower list changed (build / upgrade / destruct, reset): write tw_inf back
+  bool en_touch;     // an enemy plane may have changed since the board was loaded (obs_dirty states the rule)
   uint64_t starts;  // start cells of roads 0-2, 16 bits each (a shift, not an indexed field: keeps U in registers)
   __device__ __forceinline__ int start(int road) const { return (int)((starts >> (16 * road)) & 0xffffu); }
   __device__ __forceinline__ void set_starts(uint32_t s0, uint32_t s1, uint32_t s2) {
@@ -214,6 +215,7 @@ __device__ __forceinline__ void load_board(Smem<NC>& S, U& u, const Ctx& x, cons
   u.progress = ddiv((double)u.steps, (double)x.C.max_episode_steps);
   u.cells_dirty = false;
   u.tw_dirty = false;
+  u.en_touch = false;
   if (x.lane < u.n && x.lane < PFE) { S.eLP[x.lane] = P.lp; S.eMg[x.lane] = P.mg; S.eInf[x.lane] = P.inf; }
   for (int i = PFE + x.lane; i < u.n; i += 64) { S.eLP[i] = a.en_lp[eb + i]; S.eMg[i] = a.en_mg[eb + i]; S.eInf[i] = a.en_inf[eb + i]; }
   uint32_t tinf = P.tinf;
@@ -249,6 +251,7 @@ __device__ __forceinline__ void reset_board(Smem<NC>& S, U& u, const Ctx& x, con
   u.atk_cd = 0; u.def_cd = 0; u.n = 0; u.nt = 0; u.ep_ret = 0.0;
   u.cells_dirty = true;
   u.tw_dirty = true;
+  u.en_touch = true;
   wsync();
 }
 

@@ -15,10 +15,22 @@ every board's float32 observation with the previous step's and prints, per board
   channels 21-24, an enemy before or after, and the always-dirty channels -- at the
   granularity of the writer's 128-B-aligned 1-KB windows (write_obs_lines), and at 128-B
   lines;
-* the share of boards with an enemy, with changed tower planes, and that ended an episode.
+* the share of boards with an enemy, with changed tower planes, and that ended an episode;
+* the windows written per board and step when the enemy class is dirty whenever the board had
+  or has an enemy (the rule up to the "enemy touched" bit), when it is dirty only if a byte of
+  the 16 enemy planes changed (what the touched bit of td_step_obs.h obs_dirty comes to, see
+  below), and the windows that hold any changed byte at all.
 
 The rule is asserted never to miss a changed byte: every differing byte lies in a window
-(and a line) the rule writes."""
+(and a line) the rule writes.
+
+``--event-envs N`` (default 160; 0 skips it) then steps N envs of the Python restatement
+(oracle.td_oracle, tests/enemyclean.py's watcher) for ``--event-steps`` steps with the default
+config and counts, over the board-steps after step 300 on which the enemy class was dirty under
+the old rule, what the kernel's bit sees: a summon, a sort that moved an enemy, a shot that
+landed, an enemy that entered a new cell -- each alone, none of them (a quiet step), how often
+the planes were in fact unchanged, and the steps without an event whose planes changed
+(asserted to be none)."""
 import argparse
 import os
 import sys
@@ -60,6 +72,8 @@ def main():
     ap.add_argument("--burnin", type=int, default=1200)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--event-envs", type=int, default=160)
+    ap.add_argument("--event-steps", type=int, default=700)
     a = ap.parse_args()
     B = a.boards
     seeds = a.seed + np.arange(B)
@@ -76,7 +90,8 @@ def main():
         bt.step(rng.randint(0, 6 * L * L + 1, size=B).astype(np.int64))
     prev = bt.obs()
     cur = np.empty_like(prev)
-    tot = {"differ": 0, WIN: 0, UPL: 0, "enemy": 0, "tower": 0, "done": 0}
+    tot = {"differ": 0, WIN: 0, UPL: 0, "enemy": 0, "tower": 0, "done": 0, "kept": 0, "same": 0, "w_old": 0, "w_new": 0,
+           "w_any": 0}
     for k in range(a.steps):
         _, done = bt.step(rng.randint(0, 6 * L * L + 1, size=B).astype(np.int64), obs=cur)
         done = done.astype(bool)
@@ -90,6 +105,12 @@ def main():
         dirty[(prev[:, 21:25] != cur[:, 21:25]).reshape(B, -1).any(axis=1)] |= COST
         dirty[enemy] |= ENEMY
         dirty[done] = 63  # a new episode: every class
+        # the same with the enemy class dirty only where a byte of the enemy planes changed
+        en_changed = (prev[:, 25:41].view(np.uint32) != cur[:, 25:41].view(np.uint32)).reshape(B, -1).any(axis=1)
+        dirty_new = dirty.copy()
+        dirty_new[enemy & ~en_changed & ~done] &= ~np.uint8(ENEMY)
+        tot["kept"] += int((enemy & ~done).sum())
+        tot["same"] += int((enemy & ~done & ~en_changed).sum())
         tot["enemy"] += int(enemy.sum())
         tot["tower"] += int((tower & ~done).sum())
         tot["done"] += int(done.sum())
@@ -100,6 +121,12 @@ def main():
                 written = (cls & dirty[b]) != 0
                 tot[size] += int(written[grp].sum()) * UB
                 assert not (uchg[b] & ~written[grp]).any(), ("the rule missed a changed byte", k, b, size)
+            cls, grp = tabs[WIN][mis[b]]
+            tot["w_old"] += int(((cls & dirty[b]) != 0).sum())
+            new = (cls & dirty_new[b]) != 0
+            tot["w_new"] += int(new.sum())
+            assert not (uchg[b] & ~new[grp]).any(), ("the changed-planes rule missed a changed byte", k, b)
+            tot["w_any"] += len(np.unique(grp[uchg[b]]))
         prev, cur = cur, prev
     n = float(B * a.steps)
     print("boards %d, burn-in %d, steps %d: per board and step" % (B, a.burnin, a.steps))
@@ -109,7 +136,36 @@ def main():
     print("  bytes that differ                      %6.0f B of %d" % (tot["differ"] / n, N4 * UB))
     print("  class rule, 1-KB line-aligned windows  %6.0f B (%.0f %%)" % (tot[WIN] / n, 100 * tot[WIN] / n / (N4 * UB)))
     print("  class rule, 128-B lines                %6.0f B (%.0f %%)" % (tot[UPL] / n, 100 * tot[UPL] / n / (N4 * UB)))
+    print("  enemy class dirty (old rule), episode kept  %5.1f %%; of those, 16 enemy planes byte-identical %5.1f %%"
+          % (100 * tot["kept"] / n, 100.0 * tot["same"] / max(tot["kept"], 1)))
+    print("  windows written, enemy class dirty with an enemy before or after   %5.2f" % (tot["w_old"] / n))
+    print("  windows written, enemy class dirty only when an enemy plane changed %5.2f" % (tot["w_new"] / n))
+    print("  windows that hold any changed byte                                  %5.2f" % (tot["w_any"] / n))
     bt.close()
+    if a.event_envs > 0:
+        events(a.event_envs, a.event_steps, a.seed)
+
+
+def events(envs, steps, seed, after=300):
+    """The kernel's enemy-touched rule on the Python restatement (module docstring)."""
+    sys.path.insert(0, os.path.join(HERE, "tests"))
+    import enemyclean as E
+    from oracle import td_oracle as O
+    tr = E.Trace(L, envs, "def", False, steps, seed0=seed, act_seed=seed, cfg=O.Config(), hp=O.Hyper())
+    ev = tr.ev[after:]
+    dirty = ((ev & E.ENDED) == 0) & (((ev & E.ENEMY) != 0) | (tr.n_en[after - 1:-1] > 0))
+    touch, planes = ev & E.TOUCH, (ev & E.PLANES) != 0
+    nd = int(dirty.sum())
+    print("Python restatement, %d envs, steps %d-%d: %d board-steps, %d with the enemy class dirty under the old rule"
+          % (envs, after, steps, ev.size, nd))
+    for name, bit in (("summon", E.SUMMON), ("shot", E.SHOT), ("move", E.MOVE), ("sort", E.SORT)):
+        print("  %-6s alone %6d" % (name, int((dirty & (touch == bit)).sum())))
+    quiet = dirty & (touch == 0)
+    print("  quiet (none of the four) %6d = %.1f %% of the dirty board-steps; planes byte-identical on %.1f %%"
+          % (int(quiet.sum()), 100.0 * quiet.sum() / max(nd, 1), 100.0 * (dirty & ~planes).sum() / max(nd, 1)))
+    missed = int((quiet & planes).sum())
+    print("  quiet steps whose enemy planes changed: %d" % missed)
+    assert missed == 0
 
 
 if __name__ == "__main__":
