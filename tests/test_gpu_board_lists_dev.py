@@ -7,7 +7,8 @@ suite pins to the oracle) with the same ids.  After every call the twins are com
 byte over ALL boards, named or not: every output tensor (sentinels in the rows never written),
 the exported state, both RNG streams, the flags, the episode records and the count of finished
 episodes (the sum of their returns is an atomic float sum: see _sum_tolerance).  Small
-handles throughout: 96 boards at L = 10, 48 at L = 20, 30 and 7.  No test provokes a fault:
+handles throughout: 96 boards at L = 10, 48 at L = 20, 30 and 7.  Lists longer than one block of
+the check kernel (2,100 boards) are in tests/test_gpu_board_lists_dev_blocks.py.  No test provokes a fault:
 every bad list is one the check kernel is specified to catch, and on a bad verdict the consumer
 reads no id.
 """
