@@ -22,6 +22,7 @@
 #include "../../include/tdstep.h"
 #include "../../include/td_diag.h"
 #include "../../include/td_diag_retained.h"
+#include "td_call_check.h"
 #include "td_cfg_check.h"
 #include "td_copy_check.h"
 #include "td_ids_check.h"
@@ -85,27 +86,20 @@ constexpr int kGuardEvery = NSLOT - 1;
 constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw does not stall the next (the HIP
                                  // runtime has 4 hardware queues per process; the step stream needs one)
 constexpr int kIdSlots = 4;      // td_copy_boards, td_step_boards: id uploads in flight before a call waits for the oldest
+// The strings the kernel-name accessors hand out: one slot each, so a name stays valid until
+// its own accessor is called again (kept_name).
+enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SLOTS };
 
 }  // namespace
 
 struct td_handle {
   int L = 0, NC = 0, B = 0, mode = 0, multi = 0, difficulty = 1, device = 0, autoreset = 1;
   int opp_np = 0;  // random_agent=False
-  int small = 0, obs_wt = 0;  // the step kernel (0 large, 1 small, 2 small2), write-through observation stores
-  int kernel_forced = 0;      // td_set_step_kernel chose the kind (else TD_KERNEL_AUTO: auto_kernel_kind)
-  // A skipping launch (a td_step into the retained buffer with StepArgs::obs_skip) runs a kind
-  // of its own (td_kernel_choice.h retained_kernel_kind): `small` stays the kind of a launch
-  // that writes every window.
-  int small_retained = 0, obs_wt_retained = 0;
-  int retained_forced = 0;    // td_set_step_kernel or td_set_retained_step_kernel chose small_retained
-  int name_kind = 0;          // the kind td_step_kernel_name names: of the last td_step's launch, else `small`
+  KernelChoice kernel;        // the step kernels of a full and of a skipping launch (td_kernel_choice.h)
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
-  std::string kernel_name;    // td_step_kernel_name
-  std::string sel_kernel_name;  // td_step_boards_kernel_name
-  std::string list_kernel_name;  // td_step_boards_dev_kernel_name
-  std::string mask_list_kernel_name;  // td_action_mask_boards_kernel_name
+  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -287,8 +281,8 @@ StepArgs base_args(td_handle* h) {
   a.xcd_map = h->xcd_map;
   a.edge_wt = h->edge_wt;
   a.opp_np = h->opp_np;
-  a.small = h->small;
-  a.obs_wt = h->obs_wt;
+  a.small = h->kernel.small;
+  a.obs_wt = h->kernel.obs_wt;
   a.obs_f16 = h->obs_fmt == TD_OBS_F16 ? 1 : 0;
   a.frame_skip = h->frame_skip;
   a.hdr = h->d_hdr; a.en_lp = h->d_en_lp; a.en_mg = h->d_en_mg; a.en_inf = h->d_en_inf;
@@ -317,45 +311,69 @@ void parallel_for(int n, F fn) {
   for (auto& t : pool) t.join();
 }
 
-// Both step kernels of the handle (0 large, 1 small, 2 small2), resolved from what was forced
-// (kernel_forced / retained_forced: h->small / h->small_retained as they stand) and the rules
-// of td_kernel_choice.h, and whether each kind's observation stores are write-through.  The
-// name goes back to the kernel of a launch that writes every window.
+// MT19937 streams as the device keeps them: OPP_WORDS per board, the 624 words and the position,
+// then the lazy boundary.  B of them, seeded by `seed` (np_seed, py_seed) from seeds[b].
+std::vector<uint32_t> seeded_streams(size_t B, const uint32_t* seeds, void (*seed)(uint32_t*, uint32_t)) {
+  std::vector<uint32_t> all(B * OPP_WORDS);
+  parallel_for((int)B, [&](int b) {
+    uint32_t* w = &all[(size_t)b * OPP_WORDS];
+    seed(w, seeds[b]);
+    w[MT_N + 1] = MT_N;  // no lazy words
+  });
+  return all;
+}
+
+// Board b's stream in the handle's array `arr` (d_opp, d_np) from or to a caller's 625 words,
+// once the device is idle.  with_hot: position and lazy boundary live in the hot record.
+int mt_put(td_handle* h, uint32_t* td_handle::*arr, int b, const uint32_t* mt) {
+  if (!h || b < 0 || b >= h->B || !mt) return fail("bad board or NULL state");
+  uint32_t w[OPP_WORDS];
+  std::memcpy(w, mt, (MT_N + 1) * 4);
+  w[MT_N + 1] = MT_N;  // no lazy words
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(h->*arr + (size_t)b * OPP_WORDS, w, sizeof w, hipMemcpyHostToDevice));
+  return 0;
+}
+int mt_get(td_handle* h, uint32_t* td_handle::*arr, int b, uint32_t* mt, bool with_hot) {
+  if (!h || b < 0 || b >= h->B || !mt) return fail("bad board or NULL state");
+  uint32_t w[OPP_WORDS], hot[HOT_WORDS];
+  HIP_OK(hipDeviceSynchronize());
+  HIP_OK(hipMemcpy(w, h->*arr + (size_t)b * OPP_WORDS, sizeof w, hipMemcpyDeviceToHost));
+  if (with_hot) {
+    HIP_OK(hipMemcpy(hot, h->d_hot + (size_t)b * HOT_WORDS, sizeof hot, hipMemcpyDeviceToHost));
+    w[MT_N] = hot[0];
+    w[MT_N + 1] = hot[1];
+  }
+  mt_finish_lazy(w);
+  std::memcpy(mt, w, (MT_N + 1) * 4);
+  return 0;
+}
+
+// Both step kernels of the handle (0 large, 1 small, 2 small2), resolved for its format and the
+// boards resident in it (td_kernel_choice.h KernelChoice::resolve).
 int apply_kernel(td_handle* h) {
   const int* r = h->resident[h->obs_fmt == TD_OBS_F16];
-  const StepKinds k = resolve_step_kinds(h->kernel_forced ? h->small : -1, h->retained_forced ? h->small_retained : -1,
-                                         h->L, h->mode, h->multi, h->obs_fmt, h->B, r[0], r[1]);
-  h->small = k.full;
-  h->small_retained = k.retained;
-  h->obs_wt = obs_write_through(k.full, h->L, h->obs_fmt, h->B);
-  h->obs_wt_retained = obs_write_through(k.retained, h->L, h->obs_fmt, h->B);
   // (while frame skip is on, td_step launches the skip kernel whatever kinds are kept here)
   // (for an aligned observation buffer: launch_step takes the large kernel for any other)
-  h->name_kind = k.full;
+  h->kernel.resolve(h->L, h->mode, h->multi, h->obs_fmt, h->B, r[0], r[1]);
   return 0;
 }
 
-// Drop staged layouts: they were drawn from a stream that has been replaced.
-int drop_staged(td_handle* h, int b) {
-  HIP_OK(hipDeviceSynchronize());
-  h->since_guard = kGuardEvery;
-  const size_t ring = (size_t)NSLOT * slot_words(h->L);
-  HIP_OK(hipMemset(h->d_nxt + (size_t)b * ring, 0, ring * 4));
-  HIP_OK(hipMemset(h->d_lay_head + b, 0, 4));
-  HIP_OK(hipMemset(h->d_lay_tail + b, 0, 4));
-  HIP_OK(hipMemset(h->d_lay_claim + b, 0, 4));
-  HIP_OK(hipMemset(h->d_scratch + (size_t)b * h->scratch_stride, 0, sizeof(RoadResume)));  // no pending draw
-  return 0;
-}
+// A ring may have lost layouts, or the boards may consume them otherwise from here on: the ring
+// guard runs before the next step, whatever its cadence.
+void guard_next_step(td_handle* h) { h->since_guard = kGuardEvery; }
 
-int drop_all_staged(td_handle* h) {
+// Drop the staged layouts of boards [b0, b0 + count): they were drawn from a stream that has been replaced.
+int drop_staged(td_handle* h, int b0, int count) {
   HIP_OK(hipDeviceSynchronize());
-  h->since_guard = kGuardEvery;
-  HIP_OK(hipMemset(h->d_nxt, 0, (size_t)h->B * NSLOT * slot_words(h->L) * 4));
-  HIP_OK(hipMemset(h->d_lay_head, 0, (size_t)h->B * 4));
-  HIP_OK(hipMemset(h->d_lay_tail, 0, (size_t)h->B * 4));
-  HIP_OK(hipMemset(h->d_lay_claim, 0, (size_t)h->B * 4));
-  HIP_OK(hipMemset(h->d_scratch, 0, (size_t)h->B * h->scratch_stride));  // no pending draws
+  guard_next_step(h);
+  const size_t ring = (size_t)NSLOT * slot_words(h->L), n = (size_t)count;
+  HIP_OK(hipMemset(h->d_nxt + (size_t)b0 * ring, 0, n * ring * 4));
+  HIP_OK(hipMemset(h->d_lay_head + b0, 0, n * 4));
+  HIP_OK(hipMemset(h->d_lay_tail + b0, 0, n * 4));
+  HIP_OK(hipMemset(h->d_lay_claim + b0, 0, n * 4));
+  // no pending draws (the RoadResume at the head of a board's scratch; the rest is a pending draw's alone)
+  HIP_OK(hipMemset(h->d_scratch + (size_t)b0 * h->scratch_stride, 0, n * h->scratch_stride));
   return 0;
 }
 
@@ -379,26 +397,38 @@ int start_refill(td_handle* h, hipStream_t s, bool after_step = false) {
   return 0;
 }
 
-int run_reset(td_handle* h, const std::vector<uint8_t>& mask, float* obs, hipStream_t s) {
-  HIP_OK(hipMemcpy(h->d_mask, mask.data(), (size_t)h->B, hipMemcpyHostToDevice));
+// The board mask of a reset or an opponent change on the device: the caller's B bytes, or every
+// board where there are none.
+int upload_mask(td_handle* h, const uint8_t* host_mask) {
+  const std::vector<uint8_t> all(host_mask ? 0 : (size_t)h->B, 1);
+  HIP_OK(hipMemcpy(h->d_mask, host_mask ? host_mask : all.data(), (size_t)h->B, hipMemcpyHostToDevice));
+  return 0;
+}
+
+// What td_reset and td_reset_layouts share: the mask, a clean failure array and the reset kernel
+// on s.  staged: the boards take the records in d_stage that d_ovr_idx names (td_reset_layouts).
+int run_reset(td_handle* h, const uint8_t* host_mask, float* obs, bool staged, hipStream_t s) {
+  if (upload_mask(h, host_mask)) return -1;
   HIP_OK(hipMemset(h->d_fail, 0, (size_t)h->B));
   StepArgs a = base_args(h);
   a.obs = obs;
   a.reset_mask = h->d_mask;
+  a.ovr_idx = staged ? h->d_ovr_idx : nullptr;
+  a.ovr_rec = staged ? h->d_stage : nullptr;
   HIP_OK(launch_reset(a, s));
-  h->since_guard = kGuardEvery;  // a reset consumed layouts: guard before the next step
-  if (h->autoreset && !h->opp_np && start_refill(h, s)) return -1;
-  HIP_OK(hipDeviceSynchronize());
+  guard_next_step(h);  // a reset consumed layouts: guard before the next step
   return 0;
 }
 
 // td_kernel_timing: the event pair of the next timed dispatch, or none once tev_cap are out.
-// td_copy_boards and td_step_boards take one whatever `every` is; td_step asks at its cadence.
+// The list calls (copies and partial steps) take one whatever `every` is; td_step asks at its
+// cadence (at_cadence: none between two timed steps).
 struct EvPair {
   hipEvent_t e0 = nullptr, e1 = nullptr;
 };
-EvPair next_timing_pair(td_handle* h) {
+EvPair next_timing_pair(td_handle* h, bool at_cadence = false) {
   EvPair p;
+  if (at_cadence && (h->steps - h->tev_from) % h->tev_every != 0) return p;
   if (h->tev_n < h->tev_cap) {
     p.e0 = h->tev[2 * (size_t)h->tev_n];
     p.e1 = h->tev[2 * (size_t)h->tev_n + 1];
@@ -437,6 +467,73 @@ int enqueue_list_check(td_handle* h, const int32_t* src, const int32_t* dst, int
   HIP_OK(launch_list_check(c, s));
   h->list_calls += 1;
   return 0;
+}
+
+// td_create's memory: the device arrays, zeroed, and the pinned id slots with their events.
+int create_memory(td_handle* h) {
+  const size_t B = (size_t)h->B;
+  for (const DevArray& a : dev_arrays(h))
+    if (dalloc(a.slot, B * a.per_board + a.fixed)) return -1;
+  if (hipHostMalloc((void**)&h->id_stage, kIdSlots * 2 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
+    return fail("td_create: %zu B of pinned host memory (td_copy_boards' index slots)", kIdSlots * 2 * B * sizeof(int32_t));
+  for (int q = 0; q < kIdSlots; ++q) HIP_OK(hipEventCreateWithFlags(&h->id_ev[q], hipEventDisableTiming));
+  return 0;
+}
+
+// Everything td_create sets up once the handle's ints are in place, in order; returns at the
+// first failure with its message (td_destroy then frees what there is).
+int create_setup(td_handle* h) {
+  const size_t B = (size_t)h->B;
+  if (create_memory(h)) {  // name the footprint (the staged-layout rings are most of it at large L)
+    const double ring = (double)B * NSLOT * slot_words(h->L) * 4.0;
+    double total = 0.0;  // everything asked for, the rings included
+    for (const DevArray& a : dev_arrays(h)) total += (double)(B * a.per_board + a.fixed);
+    std::string e = g_err;
+    return fail("td_create: %d boards at L = %d need %.1f MB of device memory (%.1f MB of it the staged-layout rings, "
+                "%d x %d words per board): %s", h->B, h->L, total / 1e6, ring / 1e6, NSLOT, slot_words(h->L), e.c_str());
+  }
+  {  // win = -1: no finished episode yet
+    std::vector<td_episode_record> init((size_t)B, td_episode_record{0.0, 0, -1});
+    HIP_OK(hipMemcpy(h->d_lastep, init.data(), B * sizeof(td_episode_record), hipMemcpyHostToDevice));
+  }
+  HIP_OK(hipMemcpy(h->d_cfg, &h->dcfg, sizeof(TdDevCfg), hipMemcpyHostToDevice));
+  {  // no defect pending; the marks are zero: no epoch (>= 1) has marked a board
+    ListState ls{};
+    ls.key = kListNoDefect;
+    HIP_OK(hipMemcpy(h->d_list, &ls, sizeof ls, hipMemcpyHostToDevice));
+  }
+  for (int q = 0; q < kSideStreams; ++q)  // side streams (layout refills)
+    HIP_OK(hipStreamCreateWithFlags(&h->side[q], hipStreamNonBlocking));
+  HIP_OK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
+  // The step-cadence refill needs the previous step finished, not its memory fenced:
+  // everything a refill reads of a step (lay_head) and publishes (slots, tags, claims,
+  // the stream) goes through write-through / atomic accesses.  Without the event's
+  // system-scope fence (a cache writeback): -0.6 % / -0.8 % per step at 8,192 / 4,096
+  // boards (profiles/r03/s17).
+  HIP_OK(hipEventCreateWithFlags(&h->ev_step, hipEventDisableTiming | hipEventDisableSystemFence));
+  {  // boards resident at once, per format and kernel: what TD_KERNEL_AUTO goes by (auto_kernel)
+    int cus = 0;
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device);
+    StepArgs ra = base_args(h);
+    for (int f = 0; f < 2; ++f) {
+      ra.obs_f16 = f;
+      h->resident[f][0] = step_resident_boards(ra, cus, 1);
+      h->resident[f][1] = step_resident_boards(ra, cus, 2);
+    }
+    if (apply_kernel(h)) return -1;
+  }
+  std::vector<uint32_t> seeds(B);
+  for (size_t b = 0; b < B; ++b) seeds[b] = (uint32_t)b;
+  return td_seed(h, seeds.data(), seeds.data());
+}
+
+// td_step_io_init, td_mask_io_init: all zero but the two header words.
+template <class IO>
+void io_init(IO* io) {
+  if (!io) return;
+  std::memset(io, 0, sizeof *io);
+  io->size = (uint32_t)sizeof(IO);
+  io->abi = TD_ABI_VERSION;
 }
 
 // td_create gives up: the handle goes, the message stays.
@@ -501,12 +598,7 @@ int td_alloc_is_contiguous(const void* p) {
   return it == g_blocks.end() ? -1 : it->second.contiguous ? 1 : 0;
 }
 
-void td_step_io_init(td_step_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof *io);
-  io->size = (uint32_t)sizeof(td_step_io);
-  io->abi = TD_ABI_VERSION;
-}
+void td_step_io_init(td_step_io* io) { io_init(io); }
 
 const char* td_last_error(void) { return g_err.c_str(); }
 
@@ -578,62 +670,7 @@ td_handle* td_create(const td_config* cfg, int map_size, int n_boards, int mode,
   h->scratch_stride = (sizeof(RoadResume) + road_scratch_bytes(map_size) + 15) & ~(size_t)15;
   h->stage_cap = std::min(n_boards, 4096);
   build_dev_cfg(*cfg, h->dcfg);
-  const size_t B = (size_t)n_boards;
-  int rc = 0;
-  for (const DevArray& a : dev_arrays(h)) rc |= dalloc(a.slot, B * a.per_board + a.fixed);
-  if (!rc && hipHostMalloc((void**)&h->id_stage, kIdSlots * 2 * B * sizeof(int32_t), hipHostMallocDefault) != hipSuccess)
-    rc = fail("td_create: %zu B of pinned host memory (td_copy_boards' index slots)", kIdSlots * 2 * B * sizeof(int32_t));
-  for (int q = 0; q < kIdSlots && !rc; ++q)
-    if (hipEventCreateWithFlags(&h->id_ev[q], hipEventDisableTiming) != hipSuccess) rc = fail("event");
-  if (rc) {  // name the footprint (the staged-layout rings are most of it at large L)
-    const double ring = (double)B * NSLOT * slot_words(map_size) * 4.0;
-    double total = 0.0;  // everything asked for, the rings included
-    for (const DevArray& a : dev_arrays(h)) total += (double)(B * a.per_board + a.fixed);
-    std::string e = g_err;
-    fail("td_create: %d boards at L = %d need %.1f MB of device memory (%.1f MB of it the staged-layout rings, "
-         "%d x %d words per board): %s", n_boards, map_size, total / 1e6, ring / 1e6, NSLOT, slot_words(map_size),
-         e.c_str());
-  }
-  if (!rc) {  // win = -1: no finished episode yet
-    std::vector<td_episode_record> init((size_t)B, td_episode_record{0.0, 0, -1});
-    if (hipMemcpy(h->d_lastep, init.data(), B * sizeof(td_episode_record), hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail("episode records init");
-  }
-  if (!rc && hipMemcpy(h->d_cfg, &h->dcfg, sizeof(TdDevCfg), hipMemcpyHostToDevice) != hipSuccess) rc = fail("cfg upload");
-  if (!rc) {  // no defect pending; the marks are zero: no epoch (>= 1) has marked a board
-    ListState ls{};
-    ls.key = kListNoDefect;
-    if (hipMemcpy(h->d_list, &ls, sizeof ls, hipMemcpyHostToDevice) != hipSuccess) rc = fail("list record init");
-  }
-  for (int q = 0; q < kSideStreams && !rc; ++q) {  // side streams (layout refills)
-    const hipError_t e = hipStreamCreateWithFlags(&h->side[q], hipStreamNonBlocking);
-    if (e != hipSuccess) rc = fail("side stream: %s", hipGetErrorString(e));
-  }
-  if (!rc && hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming) != hipSuccess) rc = fail("event");
-  {
-    // The step-cadence refill needs the previous step finished, not its memory fenced:
-    // everything a refill reads of a step (lay_head) and publishes (slots, tags, claims,
-    // the stream) goes through write-through / atomic accesses.  Without the event's
-    // system-scope fence (a cache writeback): -0.6 % / -0.8 % per step at 8,192 / 4,096
-    // boards (profiles/r03/s17).
-    const unsigned fl = hipEventDisableTiming | hipEventDisableSystemFence;
-    if (!rc && hipEventCreateWithFlags(&h->ev_step, fl) != hipSuccess) rc = fail("event");
-  }
-  if (rc) return create_failed(h);
-  {  // boards resident at once, per format and kernel: what TD_KERNEL_AUTO goes by (auto_kernel)
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    StepArgs ra = base_args(h);
-    for (int f = 0; f < 2; ++f) {
-      ra.obs_f16 = f;
-      h->resident[f][0] = step_resident_boards(ra, cus, 1);
-      h->resident[f][1] = step_resident_boards(ra, cus, 2);
-    }
-    if (apply_kernel(h)) return create_failed(h);
-  }
-  std::vector<uint32_t> seeds(B);
-  for (size_t b = 0; b < B; ++b) seeds[b] = (uint32_t)b;
-  if (td_seed(h, seeds.data(), seeds.data()) != 0) return create_failed(h);
+  if (create_setup(h)) return create_failed(h);
   {
     std::lock_guard<std::mutex> g(g_handles_mu);
     g_handles.insert(h);
@@ -721,7 +758,7 @@ int td_set_autoreset(td_handle* h, int on) {
   if (!h) return fail("NULL handle");
   HIP_OK(hipDeviceSynchronize());
   h->autoreset = on ? 1 : 0;
-  h->since_guard = kGuardEvery;
+  guard_next_step(h);
   return 0;
 }
 
@@ -735,7 +772,7 @@ int td_set_random_agent(td_handle* h, int random_agent) {
     return fail("random_agent=False: not supported with frame skip (td_frame_skip() = %d); set td_set_frame_skip(h, 1) first",
                 h->frame_skip);
   HIP_OK(hipDeviceSynchronize());
-  h->since_guard = kGuardEvery;
+  guard_next_step(h);
   if (!random_agent && !h->opp_np) {
     std::vector<uint32_t> head((size_t)h->B), tail((size_t)h->B);
     HIP_OK(hipMemcpy(head.data(), h->d_lay_head, (size_t)h->B * 4, hipMemcpyDeviceToHost));
@@ -756,22 +793,12 @@ int td_seed(td_handle* h, const uint32_t* np_seeds, const uint32_t* py_seeds) {
   if (!h) return fail("NULL handle");
   const size_t B = (size_t)h->B;
   if (np_seeds) {
-    std::vector<uint32_t> nw(B * OPP_WORDS);
-    parallel_for((int)B, [&](int b) {
-      uint32_t* w = &nw[(size_t)b * OPP_WORDS];
-      np_seed(w, np_seeds[b]);
-      w[MT_N + 1] = MT_N;  // no lazy words
-    });
-    if (drop_all_staged(h)) return -1;
+    const std::vector<uint32_t> nw = seeded_streams(B, np_seeds, np_seed);
+    if (drop_staged(h, 0, h->B)) return -1;
     HIP_OK(hipMemcpy(h->d_np, nw.data(), B * OPP_WORDS * 4, hipMemcpyHostToDevice));
   }
   if (py_seeds) {
-    std::vector<uint32_t> op(B * OPP_WORDS);
-    parallel_for((int)B, [&](int b) {
-      uint32_t* w = &op[(size_t)b * OPP_WORDS];
-      py_seed(w, py_seeds[b]);
-      w[MT_N + 1] = MT_N;  // no lazy words
-    });
+    const std::vector<uint32_t> op = seeded_streams(B, py_seeds, py_seed);
     std::vector<uint32_t> hot(B * HOT_WORDS, 0u);
     for (size_t b = 0; b < B; ++b) { hot[b * HOT_WORDS] = MT_N; hot[b * HOT_WORDS + 1] = MT_N; }
     HIP_OK(hipDeviceSynchronize());
@@ -782,64 +809,34 @@ int td_seed(td_handle* h, const uint32_t* np_seeds, const uint32_t* py_seeds) {
 }
 
 int td_set_py_state(td_handle* h, int b, const uint32_t* mt) {
-  if (!h || b < 0 || b >= h->B || !mt) return fail("bad board or NULL state");
-  uint32_t w[OPP_WORDS];
-  std::memcpy(w, mt, (MT_N + 1) * 4);
-  w[MT_N + 1] = MT_N;
-  uint32_t hot[HOT_WORDS] = {w[MT_N], MT_N, 0u};
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(h->d_opp + (size_t)b * OPP_WORDS, w, sizeof w, hipMemcpyHostToDevice));
+  if (mt_put(h, &td_handle::d_opp, b, mt)) return -1;
+  const uint32_t hot[HOT_WORDS] = {mt[MT_N], MT_N, 0u};
   HIP_OK(hipMemcpy(h->d_hot + (size_t)b * HOT_WORDS, hot, sizeof hot, hipMemcpyHostToDevice));
   return 0;
 }
 // The device keeps the opponent's position in the hot record and may have
 // pre-drawn (and lazily twisted) ahead of it; the exported state is CPython's
 // getstate() form of the same stream (equal future draws).
-int td_get_py_state(td_handle* h, int b, uint32_t* mt) {
-  if (!h || b < 0 || b >= h->B || !mt) return fail("bad board or NULL state");
-  uint32_t w[OPP_WORDS], hot[HOT_WORDS];
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(w, h->d_opp + (size_t)b * OPP_WORDS, sizeof w, hipMemcpyDeviceToHost));
-  HIP_OK(hipMemcpy(hot, h->d_hot + (size_t)b * HOT_WORDS, sizeof hot, hipMemcpyDeviceToHost));
-  w[MT_N] = hot[0];
-  w[MT_N + 1] = hot[1];
-  mt_finish_lazy(w);
-  std::memcpy(mt, w, (MT_N + 1) * 4);
-  return 0;
-}
-int td_get_np_state(td_handle* h, int b, uint32_t* mt) {
-  if (!h || b < 0 || b >= h->B || !mt) return fail("bad board or NULL state");
-  uint32_t w[OPP_WORDS];
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(w, h->d_np + (size_t)b * OPP_WORDS, sizeof w, hipMemcpyDeviceToHost));
-  mt_finish_lazy(w);
-  std::memcpy(mt, w, (MT_N + 1) * 4);
-  return 0;
-}
+int td_get_py_state(td_handle* h, int b, uint32_t* mt) { return mt_get(h, &td_handle::d_opp, b, mt, true); }
+int td_get_np_state(td_handle* h, int b, uint32_t* mt) { return mt_get(h, &td_handle::d_np, b, mt, false); }
 int td_set_np_state(td_handle* h, int b, const uint32_t* mt) {
-  if (!h || b < 0 || b >= h->B || !mt) return fail("bad board or NULL state");
-  uint32_t w[OPP_WORDS];
-  std::memcpy(w, mt, (MT_N + 1) * 4);
-  w[MT_N + 1] = MT_N;
-  HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(h->d_np + (size_t)b * OPP_WORDS, w, sizeof w, hipMemcpyHostToDevice));
-  return drop_staged(h, b);
+  return mt_put(h, &td_handle::d_np, b, mt) ? -1 : drop_staged(h, b, 1);
 }
 
 int td_reset(td_handle* h, const uint8_t* host_mask, float* obs, void* stream) {
   if (!h) return fail("NULL handle");
   hipStream_t s = (hipStream_t)stream;
-  std::vector<uint8_t> mask((size_t)h->B, 1);
-  if (host_mask) std::memcpy(mask.data(), host_mask, (size_t)h->B);
   HIP_OK(hipDeviceSynchronize());
   const bool mine = h->ledger.reset_into(obs);
   ObsLedger::Guard guard{&h->ledger};
-  if (run_reset(h, mask, obs, s)) return -1;
+  if (run_reset(h, host_mask, obs, false, s)) return -1;
+  if (h->autoreset && !h->opp_np && start_refill(h, s)) return -1;
+  HIP_OK(hipDeviceSynchronize());
   std::vector<uint8_t> fl((size_t)h->B);
   HIP_OK(hipMemcpy(fl.data(), h->d_fail, (size_t)h->B, hipMemcpyDeviceToHost));
   h->last_reset_failed.clear();
   for (int b = 0; b < h->B; ++b) {
-    if (!mask[(size_t)b]) continue;
+    if (host_mask && !host_mask[(size_t)b]) continue;
     if (fl[(size_t)b]) h->last_reset_failed.push_back(b);
     else if (mine) h->ledger.mark(b);  // (a board whose draw failed keeps its state, and its observation)
   }
@@ -879,15 +876,7 @@ int td_reset_layouts(td_handle* h, const uint32_t* recs, const int32_t* boards, 
     for (int i = 0; i < m; ++i) { idx[(size_t)boards[i0 + i]] = i; mask[(size_t)boards[i0 + i]] = 1; }
     HIP_OK(hipMemcpy(h->d_stage, recs + (size_t)i0 * h->lw, (size_t)m * h->lw * 4, hipMemcpyHostToDevice));
     HIP_OK(hipMemcpy(h->d_ovr_idx, idx.data(), (size_t)h->B * 4, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(h->d_mask, mask.data(), (size_t)h->B, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(h->d_fail, 0, (size_t)h->B));
-    StepArgs a = base_args(h);
-    a.obs = obs;
-    a.reset_mask = h->d_mask;
-    a.ovr_idx = h->d_ovr_idx;
-    a.ovr_rec = h->d_stage;
-    HIP_OK(launch_reset(a, s));
-    h->since_guard = kGuardEvery;
+    if (run_reset(h, mask.data(), obs, true, s)) return -1;
     HIP_OK(hipStreamSynchronize(s));
     for (int i = 0; mine && i < m; ++i) h->ledger.mark(boards[i0 + i]);
   }
@@ -968,6 +957,28 @@ int before_step_launch(td_handle* h, const StepArgs& a, hipStream_t s) {
   return 0;
 }
 
+// What a stepping launch leaves behind, whether it stepped every board or some: one more launch
+// for the refill cadence and td_kernel_timing's, one more since the ring guard.
+void step_launched(td_handle* h) {
+  h->steps += 1;
+  h->since_guard += 1;
+}
+
+// check_step_io, then what a partial step asks of the handle's settings (td_call_check.h).
+int check_partial_step(const char* fn, const td_handle* h, const td_step_io* io) {
+  if (check_step_io(fn, h, io)) return -1;
+  char msg[240];
+  return partial_step_refused(fn, h->frame_skip, h->opp_np, h->autoreset, msg, sizeof msg) ? fail("%s", msg) : 0;
+}
+
+// A device list's cap and pointers against B boards (td_call_check.h list_args_check): 1 go on,
+// 0 an empty list (the call returns 0), -1 refused.  B = 0 where a call has no handle yet: cap < 0.
+int check_list_args(const char* fn, int cap, int B, bool have_lists, const char* lists) {
+  char msg[200];
+  const int go = list_args_check(fn, cap, B, have_lists, lists, msg, sizeof msg);
+  return go == LIST_ARGS_REFUSED ? fail("%s", msg) : go;
+}
+
 }  // namespace
 
 int td_step(td_handle* h, const td_step_io* io, void* stream) {
@@ -980,7 +991,7 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   a.obs_skip = h->ledger.full_step_skips(io->obs) ? 1 : 0;
   ObsLedger::Guard guard{&h->ledger};
   if (before_step_launch(h, a, s)) return -1;
-  const EvPair ev = (h->steps - h->tev_from) % h->tev_every == 0 ? next_timing_pair(h) : EvPair{};
+  const EvPair ev = next_timing_pair(h, true);
   // frame skip: one launch of the skip kernel runs the k board steps (td_step_skip.h).  The refill
   // cadence and the ring guard above count launches: a board consumes at most one layout per launch.
   if (h->frame_skip > 1) {
@@ -988,15 +999,13 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
   } else {
     // the kernel is chosen per launch: a launch that writes every window is bound by its stores,
     // a skipping launch by the boards in flight (td_kernel_choice.h retained_kernel_kind)
-    const int kind = a.obs_skip ? h->small_retained : h->small;
-    a.small = kind;
-    a.obs_wt = a.obs_skip ? h->obs_wt_retained : h->obs_wt;
-    HIP_OK(launch_step(a, kind, s, ev.e0, ev.e1));
-    h->name_kind = step_launch_kind(a, kind);
+    a.small = h->kernel.kind(a.obs_skip);
+    a.obs_wt = h->kernel.write_through(a.obs_skip);
+    HIP_OK(launch_step(a, a.small, s, ev.e0, ev.e1));
+    h->kernel.name_kind = step_launch_kind(a, a.small);
   }
   if (h->autoreset && h->opp_np) HIP_OK(launch_autoreset(a, s));
-  h->steps += 1;
-  h->since_guard += 1;
+  step_launched(h);
   if (!retained) h->ledger.touch();
   else if (!a.obs_skip) h->ledger.mark_all();  // every board's observation is in the retained buffer now
   guard.ok = true;
@@ -1008,13 +1017,7 @@ int td_step(td_handle* h, const td_step_io* io, void* stream) {
 // the ids reach the kernel through the pinned id slots and d_pairs (upload_ids), so the caller's
 // array is free on return.
 int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, int n, void* stream) {
-  if (check_step_io("td_step_boards", h, io)) return -1;
-  if (h->frame_skip > 1)
-    return fail("td_step_boards: not supported with frame skip (td_frame_skip() = %d); set td_set_frame_skip(h, 1) first",
-                h->frame_skip);
-  if (h->opp_np && h->autoreset)
-    return fail("td_step_boards: not supported with random_agent = 0 and auto-reset on (the reset kernel behind a step "
-                "goes by done[] of every board, and an unnamed board's is stale)");
+  if (check_partial_step("td_step_boards", h, io)) return -1;
   char msg[200];
   if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("td_step_boards: %s", msg);
   if (n == 0) return 0;
@@ -1030,8 +1033,7 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
   if (before_step_launch(h, a, s) || upload_ids(h, boards, nullptr, n, s)) return -1;
   const EvPair ev = next_timing_pair(h);  // whatever `every` is (as the copy's)
   HIP_OK(launch_step_sel(a, h->d_pairs, n, s, ev.e0, ev.e1));
-  h->steps += 1;
-  h->since_guard += 1;
+  step_launched(h);
   if (!retained) h->ledger.touch();
   else
     for (int i = 0; !known && i < n; ++i) h->ledger.mark(boards[i]);  // written whole just now
@@ -1044,19 +1046,12 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
 // front of the list kernel; nothing is brought to the host and nothing is waited for.
 int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards_dev, int cap, const int32_t* count_dev,
                        td_list_status* status_dev, void* stream) {
+  const char* fn = "td_step_boards_dev";
   // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
   if (io && io->size == (uint32_t)sizeof(td_step_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
-    return fail("td_step_boards_dev: cap = %d is negative", cap);
-  if (check_step_io("td_step_boards_dev", h, io)) return -1;
-  if (h->frame_skip > 1)
-    return fail("td_step_boards_dev: not supported with frame skip (td_frame_skip() = %d); set td_set_frame_skip(h, 1) "
-                "first", h->frame_skip);
-  if (h->opp_np && h->autoreset)
-    return fail("td_step_boards_dev: not supported with random_agent = 0 and auto-reset on (the reset kernel behind a "
-                "step goes by done[] of every board, and an unnamed board's is stale)");
-  if (cap > h->B) return fail("td_step_boards_dev: cap = %d outside [0, %d] (the handle's boards)", cap, h->B);
-  if (cap == 0) return 0;
-  if (!boards_dev) return fail("td_step_boards_dev: boards_dev is NULL with cap = %d", cap);
+    return check_list_args(fn, cap, 0, false, "");
+  if (check_partial_step(fn, h, io)) return -1;
+  if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
   hipStream_t s = (hipStream_t)stream;
   StepArgs a = step_args(h, io);
   // td_retain_obs: which boards the list names is not known here, so the kernel skips clean
@@ -1067,8 +1062,7 @@ int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards
   if (before_step_launch(h, a, s) || enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
   const EvPair ev = next_timing_pair(h);  // the consumer's, whatever `every` is (as td_step_boards')
   HIP_OK(launch_step_list(a, boards_dev, cap, count_dev, &h->d_list->verdict, s, ev.e0, ev.e1));
-  h->steps += 1;
-  h->since_guard += 1;
+  step_launched(h);
   h->ledger.list_call_into(io->obs);
   guard.ok = true;
   return 0;
@@ -1077,11 +1071,10 @@ int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards
 // td_copy_boards for lists, their length and their verdict in device memory (see above).
 int td_copy_boards_dev(td_handle* h, const int32_t* src_dev, const int32_t* dst_dev, int cap, const int32_t* count_dev,
                        float* obs, td_list_status* status_dev, void* stream) {
-  if (cap < 0) return fail("td_copy_boards_dev: cap = %d is negative", cap);  // (needs no handle)
-  if (!h) return fail("td_copy_boards_dev: NULL handle");
-  if (cap > h->B) return fail("td_copy_boards_dev: cap = %d outside [0, %d] (the handle's boards)", cap, h->B);
-  if (cap == 0) return 0;
-  if (!src_dev || !dst_dev) return fail("td_copy_boards_dev: src_dev or dst_dev is NULL with cap = %d", cap);
+  const char* fn = "td_copy_boards_dev";
+  if (cap < 0) return check_list_args(fn, cap, 0, false, "");  // (needs no handle)
+  if (!h) return fail("%s: NULL handle", fn);
+  if (const int go = check_list_args(fn, cap, h->B, src_dev && dst_dev, "src_dev or dst_dev"); go <= 0) return go;
   hipStream_t s = (hipStream_t)stream;
   ObsLedger::Guard guard{&h->ledger};
   if (enqueue_list_check(h, src_dev, dst_dev, cap, count_dev, status_dev, s)) return -1;
@@ -1109,24 +1102,21 @@ int td_list_errors(td_handle* h, td_list_status* first, int clear) {
   return (int)std::min<uint32_t>(ls.refused, 0x7fffffffu);
 }
 
+// A kernel's name for its accessor: kept in the accessor's slot of the handle.
+static const char* kept_name(td_handle* h, int slot, const std::string& name) {
+  h->names[slot] = name;
+  return h->names[slot].c_str();
+}
+
 const char* td_step_boards_dev_kernel_name(td_handle* h) {
-  if (!h) return "";
-  h->list_kernel_name = kernel_display_name(list_row(base_args(h)));
-  return h->list_kernel_name.c_str();
+  return h ? kept_name(h, NAME_LIST, kernel_display_name(list_row(base_args(h)))) : "";
 }
 
 const char* td_step_boards_kernel_name(td_handle* h) {
-  if (!h) return "";
-  h->sel_kernel_name = kernel_display_name(sel_row(base_args(h)));
-  return h->sel_kernel_name.c_str();
+  return h ? kept_name(h, NAME_SEL, kernel_display_name(sel_row(base_args(h)))) : "";
 }
 
-void td_mask_io_init(td_mask_io* io) {
-  if (!io) return;
-  std::memset(io, 0, sizeof *io);
-  io->size = (uint32_t)sizeof(td_mask_io);
-  io->abi = TD_ABI_VERSION;
-}
+void td_mask_io_init(td_mask_io* io) { io_init(io); }
 
 namespace {
 
@@ -1190,14 +1180,13 @@ int td_action_mask_boards(td_handle* h, const td_mask_io* io, const int32_t* boa
 // front of the mask kernel; a refused list writes no output byte.
 int td_action_mask_boards_dev(td_handle* h, const td_mask_io* io, const int32_t* boards_dev, int cap,
                               const int32_t* count_dev, td_list_status* status_dev, void* stream) {
+  const char* fn = "td_action_mask_boards_dev";
   // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
   if (io && io->size == (uint32_t)sizeof(td_mask_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
-    return fail("td_action_mask_boards_dev: cap = %d is negative", cap);
+    return check_list_args(fn, cap, 0, false, "");
   MaskArgs a;
-  if (check_mask_io("td_action_mask_boards_dev", h, io, &a)) return -1;
-  if (cap > h->B) return fail("td_action_mask_boards_dev: cap = %d outside [0, %d] (the handle's boards)", cap, h->B);
-  if (cap == 0) return 0;
-  if (!boards_dev) return fail("td_action_mask_boards_dev: boards_dev is NULL with cap = %d", cap);
+  if (check_mask_io(fn, h, io, &a)) return -1;
+  if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
   hipStream_t s = (hipStream_t)stream;
   if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
   HIP_OK(launch_mask_list(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
@@ -1208,39 +1197,32 @@ const char* td_action_mask_boards_kernel_name(td_handle* h) {
   if (!h) return "";
   char buf[64];
   std::snprintf(buf, sizeof buf, "td_mask_list_kernel<%d>", with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
-  h->mask_list_kernel_name = buf;
-  return h->mask_list_kernel_name.c_str();
+  return kept_name(h, NAME_MASK_LIST, buf);
+}
+
+// Both kernel-kind setters: the kind is checked against the map side (td_kernel_choice.h
+// kernel_kind_ok), forced for both kinds of launch or for skipping launches only
+// (KernelChoice::force_both, force_retained), and the kinds are resolved again.
+static int set_kernel_kind(const char* fn, td_handle* h, int kind, void (KernelChoice::*force)(int)) {
+  if (!h) return fail("NULL handle");
+  char msg[200];
+  if (!kernel_kind_ok(fn, kind, h->L, msg, sizeof msg)) return fail("%s", msg);
+  HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
+  (h->kernel.*force)(kind);
+  return apply_kernel(h);
 }
 
 int td_set_step_kernel(td_handle* h, int kind) {
-  if (!h) return fail("NULL handle");
-  if (kind < TD_KERNEL_AUTO || kind > TD_KERNEL_SMALL2) return fail("td_set_step_kernel: unknown kernel kind %d", kind);
-  if (kind >= TD_KERNEL_SMALL && h->L != 10 && h->L != 20 && h->L != 30)
-    return fail("td_set_step_kernel: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", h->L);
-  HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
-  // a forced kind is forced for every launch, skipping or not; TD_KERNEL_AUTO gives both back to their rules
-  h->kernel_forced = h->retained_forced = kind != TD_KERNEL_AUTO;
-  if (kind != TD_KERNEL_AUTO) h->small = h->small_retained = kind - 1;
-  return apply_kernel(h);
+  return set_kernel_kind("td_set_step_kernel", h, kind, &KernelChoice::force_both);
 }
 
-// Skipping launches only: TD_KERNEL_AUTO gives their kind back to the rule (on the full kind as
-// it stands, forced or not), any other kind forces it.  The kind of a launch that writes every
-// window stays.
 int td_set_retained_step_kernel(td_handle* h, int kind) {
-  if (!h) return fail("NULL handle");
-  if (kind < TD_KERNEL_AUTO || kind > TD_KERNEL_SMALL2) return fail("td_set_retained_step_kernel: unknown kernel kind %d", kind);
-  if (kind >= TD_KERNEL_SMALL && h->L != 10 && h->L != 20 && h->L != 30)
-    return fail("td_set_retained_step_kernel: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", h->L);
-  HIP_OK(hipDeviceSynchronize());  // launches already queued keep the kernel they were enqueued with
-  h->retained_forced = kind != TD_KERNEL_AUTO;
-  if (kind != TD_KERNEL_AUTO) h->small_retained = kind - 1;
-  return apply_kernel(h);
+  return set_kernel_kind("td_set_retained_step_kernel", h, kind, &KernelChoice::force_retained);
 }
 
-int td_step_kernel(td_handle* h) { return h ? h->small + 1 : fail("NULL handle"); }
+int td_step_kernel(td_handle* h) { return h ? h->kernel.small + 1 : fail("NULL handle"); }
 
-int td_retained_step_kernel(td_handle* h) { return h ? h->small_retained + 1 : fail("NULL handle"); }
+int td_retained_step_kernel(td_handle* h) { return h ? h->kernel.small_retained + 1 : fail("NULL handle"); }
 
 // The observation's element.  A kernel kind the caller forced stays, TD_KERNEL_AUTO is
 // resolved again for the new format (apply_kernel), for both kinds of launch; the write-through
@@ -1290,8 +1272,7 @@ const void* td_retained_obs(td_handle* h) { return h ? h->ledger.retained : null
 const char* td_step_kernel_name(td_handle* h) {
   if (!h) return "";
   const StepArgs a = base_args(h);
-  h->kernel_name = kernel_display_name(h->frame_skip > 1 ? skip_row(a) : step_row(a, h->name_kind));
-  return h->kernel_name.c_str();
+  return kept_name(h, NAME_STEP, kernel_display_name(h->frame_skip > 1 ? skip_row(a) : step_row(a, h->kernel.name_kind)));
 }
 
 int td_set_refill_interval(td_handle* h, int steps) {
@@ -1346,10 +1327,8 @@ int td_opponent(td_handle* h, int side, int level, const uint8_t* host_mask, voi
   if (side == 1 && (level < 0 || level > 2)) return fail("td_opponent: random_tower_lv%d does not exist", level);
   if (side != 0 && side != 1) return fail("td_opponent: side must be 0 (enemy) or 1 (tower)");
   hipStream_t s = (hipStream_t)stream;
-  std::vector<uint8_t> mask((size_t)h->B, 1);
-  if (host_mask) std::memcpy(mask.data(), host_mask, (size_t)h->B);
   HIP_OK(hipDeviceSynchronize());
-  HIP_OK(hipMemcpy(h->d_mask, mask.data(), (size_t)h->B, hipMemcpyHostToDevice));
+  if (upload_mask(h, host_mask)) return -1;
   StepArgs a = base_args(h);
   a.reset_mask = h->d_mask;
   h->ledger.touch();  // enemies, towers and costs change; no observation is written

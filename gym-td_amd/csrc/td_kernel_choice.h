@@ -1,9 +1,14 @@
 // td_kernel_choice.h -- which step kernel TD_KERNEL_AUTO means, and when its observation
-// stores are write-through.  Plain C++, no HIP: functions of the handle's ints, which
-// td_capi.hip calls (auto_kernel, apply_kernel) and scripts/kernel_choice_host.cpp runs
-// alone, boundary by boundary.  Kinds: 0 large, 1 small, 2 small2 (td_handle.small).
+// stores are write-through, and the record a handle keeps of its choice (KernelChoice).  Plain
+// C++, no HIP: functions of the handle's ints, which td_capi.hip calls (apply_kernel, the two
+// kernel-kind setters, td_step) and scripts/kernel_choice_host.cpp and
+// scripts/retained_kernel_host.cpp run alone, boundary by boundary and setter by setter.
+// Kinds: 0 large, 1 small, 2 small2 (KernelChoice::small).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+#include <cstdio>
 
 #include "../../include/tdstep.h"
 #include "td_common.h"
@@ -81,23 +86,6 @@ inline int retained_kernel_kind(int L, int mode, int multi, int obs_fmt, int B, 
   return full_kind;
 }
 
-// Both kinds of a handle.  forced_full / forced_retained: a kind the caller forced (0 .. 2),
-// or -1 for TD_KERNEL_AUTO.  td_set_step_kernel forces both (a forced kind is forced for every
-// launch), td_set_retained_step_kernel the second only; an unforced retained kind follows the
-// rule on the full kind as resolved, forced or not.
-struct StepKinds {
-  int full, retained;
-};
-inline StepKinds resolve_step_kinds(int forced_full, int forced_retained, int L, int mode, int multi, int obs_fmt, int B,
-                                    int resident, int resident2) {
-  StepKinds k;
-  k.full = forced_full >= 0 ? forced_full : auto_kernel_kind(L, mode, multi, obs_fmt, B, resident, resident2);
-  k.retained = forced_retained >= 0
-                   ? forced_retained
-                   : retained_kernel_kind(L, mode, multi, obs_fmt, B, resident, resident2, k.full);
-  return k;
-}
-
 // Write-through observation stores go with the small kernels where the batch's observation
 // fits the 256-MiB Infinity Cache (scripts/storepol.hip: 21.8 vs 30.0 us at 8,192 boards).
 // (Write-through beyond the Infinity Cache -- any kernel, TD_OBS_WT=1 -- measured 1.5-1.7x
@@ -107,5 +95,59 @@ inline int obs_write_through(int kind, int L, int obs_fmt, int B) {
   const double obs_bytes = (double)B * NCH * (L * L) * (f16 ? 2.0 : 4.0);
   return kind && obs_bytes <= 192.0 * 1024 * 1024 ? 1 : 0;
 }
+
+// What td_set_step_kernel and td_set_retained_step_kernel refuse of a kind (TD_KERNEL_AUTO ..
+// TD_KERNEL_SMALL2) on a map side L.  fn: the caller's name, for the message.
+inline bool kernel_kind_ok(const char* fn, int kind, int L, char* msg, size_t cap) {
+  if (kind < TD_KERNEL_AUTO || kind > TD_KERNEL_SMALL2)
+    std::snprintf(msg, cap, "%s: unknown kernel kind %d", fn, kind);
+  else if (kind >= TD_KERNEL_SMALL && L != 10 && L != 20 && L != 30)
+    std::snprintf(msg, cap, "%s: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", fn, L);
+  else
+    return true;
+  return false;
+}
+
+// A handle's kernel choice, as one record (td_handle.kernel): both kinds of a handle.
+// td_set_step_kernel forces both (a forced kind is forced for every launch),
+// td_set_retained_step_kernel the second only; an unforced retained kind follows the rule on the
+// full kind as resolved, forced or not.
+struct KernelChoice {
+  int small = 0, obs_wt = 0;  // the step kernel (0 large, 1 small, 2 small2), write-through observation stores
+  int kernel_forced = 0;      // td_set_step_kernel chose the kind (else TD_KERNEL_AUTO: auto_kernel_kind)
+  // A skipping launch (a td_step into the retained buffer with StepArgs::obs_skip) runs a kind
+  // of its own (retained_kernel_kind): `small` stays the kind of a launch that writes every window.
+  int small_retained = 0, obs_wt_retained = 0;
+  int retained_forced = 0;    // td_set_step_kernel or td_set_retained_step_kernel chose small_retained
+  int name_kind = 0;          // the kind td_step_kernel_name names: of the last td_step's launch, else `small`
+
+  // td_set_step_kernel (kind as kernel_kind_ok passed it):
+  // a forced kind is forced for every launch, skipping or not; TD_KERNEL_AUTO gives both back to their rules
+  void force_both(int kind) {
+    kernel_forced = retained_forced = kind != TD_KERNEL_AUTO;
+    if (kind != TD_KERNEL_AUTO) small = small_retained = kind - 1;
+  }
+  // td_set_retained_step_kernel: skipping launches only.  TD_KERNEL_AUTO gives their kind back to
+  // the rule (on the full kind as it stands, forced or not), any other kind forces it.  The kind
+  // of a launch that writes every window stays.
+  void force_retained(int kind) {
+    retained_forced = kind != TD_KERNEL_AUTO;
+    if (kind != TD_KERNEL_AUTO) small_retained = kind - 1;
+  }
+  // Both kinds, resolved: a forced kind stays as it stands, any other follows its rule above;
+  // then whether each kind's observation stores are write-through.  The name goes back to the
+  // kernel of a launch that writes every window.
+  void resolve(int L, int mode, int multi, int obs_fmt, int B, int resident, int resident2) {
+    if (!kernel_forced) small = auto_kernel_kind(L, mode, multi, obs_fmt, B, resident, resident2);
+    if (!retained_forced) small_retained = retained_kernel_kind(L, mode, multi, obs_fmt, B, resident, resident2, small);
+    obs_wt = obs_write_through(small, L, obs_fmt, B);
+    obs_wt_retained = obs_write_through(small_retained, L, obs_fmt, B);
+    name_kind = small;
+  }
+  // The kernel is chosen per launch: a launch that writes every window is bound by its stores,
+  // a skipping launch by the boards in flight (retained_kernel_kind).
+  int kind(int obs_skip) const { return obs_skip ? small_retained : small; }
+  int write_through(int obs_skip) const { return obs_skip ? obs_wt_retained : obs_wt; }
+};
 
 }  // namespace td

@@ -1,7 +1,8 @@
 // retained_kernel_host.cpp -- the kind of a skipping launch (gym-td_amd/csrc/td_kernel_choice.h
-// retained_kernel_kind) at every boundary of its table, and the order in which a handle's two
-// kinds are resolved (resolve_step_kinds: forced versus TD_KERNEL_AUTO), as a host program of its
-// own: no HIP, no Python, no GPU.  The rule decides which kernel the bench's timed steps run; a
+// retained_kernel_kind) at every boundary of its table, the order in which a handle's two
+// kinds are resolved (KernelChoice::resolve: forced versus TD_KERNEL_AUTO), and what the two
+// kernel-kind setters do to the record (KernelChoice::force_both, force_retained, kernel_kind_ok),
+// as a host program of its own: no HIP, no Python, no GPU.  The rule decides which kernel the bench's timed steps run; a
 // boundary one board off would pass every parity test and show only as a slower step.
 //
 //   c++ -std=c++17 -g -O1 -fsanitize=address,undefined -fno-sanitize-recover=all
@@ -12,6 +13,7 @@
 // L = 10 (256 CUs x 4 SIMDs x 8 waves), half of them at L = 20 / 30.
 // Prints "retained_kernel: N cases ok" and returns 0, or names the first case that went wrong.
 #include <cstdio>
+#include <cstring>
 #include <initializer_list>
 
 #define __host__
@@ -35,12 +37,47 @@ void expect_retained(int fmt, int L, int mode, int multi, int r1, int r2, int B,
 
 void expect_kinds(int ff, int fr, int fmt, int L, int mode, int multi, int r1, int r2, int B, int want_full,
                   int want_retained) {
-  const td::StepKinds k = td::resolve_step_kinds(ff, fr, L, mode, multi, fmt, B, r1, r2);
+  td::KernelChoice k;  // forced as the setters leave it: the flag, and the kind in its place
+  k.kernel_forced = ff >= 0;
+  k.retained_forced = fr >= 0;
+  if (ff >= 0) k.small = ff;
+  if (fr >= 0) k.small_retained = fr;
+  k.resolve(L, mode, multi, fmt, B, r1, r2);
   ++g_cases;
-  if ((k.full != want_full || k.retained != want_retained) && !g_bad++)
-    std::printf("FAIL kinds: forced %d / %d %s L %d %s %s B %d: got %d / %d want %d / %d\n", ff, fr,
-                fmt ? "float16" : "float32", L, kModes[mode], multi ? "multi-action" : "single action", B, k.full,
-                k.retained, want_full, want_retained);
+  const bool wt_ok = k.obs_wt == td::obs_write_through(k.small, L, fmt, B) &&
+                     k.obs_wt_retained == td::obs_write_through(k.small_retained, L, fmt, B) && k.name_kind == k.small &&
+                     k.kind(0) == k.small && k.kind(1) == k.small_retained && k.write_through(0) == k.obs_wt &&
+                     k.write_through(1) == k.obs_wt_retained;
+  if ((k.small != want_full || k.small_retained != want_retained || !wt_ok) && !g_bad++)
+    std::printf("FAIL kinds: forced %d / %d %s L %d %s %s B %d: got %d / %d want %d / %d (flags ok %d)\n", ff, fr,
+                fmt ? "float16" : "float32", L, kModes[mode], multi ? "multi-action" : "single action", B, k.small,
+                k.small_retained, want_full, want_retained, (int)wt_ok);
+}
+
+// One step of a setter sequence on a TD-def 10x10 handle of 65,536 boards (rules: small2 / small):
+// the setter, then the resolve td_capi.hip's apply_kernel runs behind it.
+struct Seq {
+  td::KernelChoice k;
+  int fmt = TD_OBS_F32;
+  void resolve() { k.resolve(10, TD_MODE_DEF, 0, fmt, 65536, 8192, 4096); }
+  void both(int kind) { k.force_both(kind); resolve(); }
+  void retained(int kind) { k.force_retained(kind); resolve(); }
+  void format(int f) { fmt = f; resolve(); }
+  void expect(const char* what, int full, int ret, int forced, int ret_forced) {
+    ++g_cases;
+    if ((k.small != full || k.small_retained != ret || k.kernel_forced != forced || k.retained_forced != ret_forced ||
+         k.name_kind != full) && !g_bad++)
+      std::printf("FAIL sequence, %s: kinds %d / %d forced %d / %d name %d, want %d / %d forced %d / %d\n", what, k.small,
+                  k.small_retained, k.kernel_forced, k.retained_forced, k.name_kind, full, ret, forced, ret_forced);
+  }
+};
+
+void expect_kind_ok(const char* fn, int kind, int L, const char* want) {
+  char msg[200] = "";
+  const bool ok = td::kernel_kind_ok(fn, kind, L, msg, sizeof msg);
+  ++g_cases;
+  if ((ok != (want[0] == 0) || std::strcmp(msg, want) != 0) && !g_bad++)
+    std::printf("FAIL kernel_kind_ok %s kind %d L %d: got %d '%s' want '%s'\n", fn, kind, L, (int)ok, msg, want);
 }
 
 }  // namespace
@@ -108,6 +145,65 @@ int main() {
   expect_kinds(0, -1, F32, 10, TD_MODE_DEF, 0, r1, r2, 8192, 0, 0);
   expect_kinds(0, -1, F32, 30, TD_MODE_DEF, 0, 4096, 2048, 16384, 0, 0);
   expect_kinds(0, -1, F16, 10, TD_MODE_DEF, 0, r1, r2, 65536, 0, 0);
+
+  // ---- the setters (kinds as the ABI numbers them: TD_KERNEL_AUTO 0, LARGE 1, SMALL 2, SMALL2 3)
+  {
+    Seq q;
+    q.resolve();
+    q.expect("as created", 2, 1, 0, 0);
+    // a forced kind survives a format change, for both kinds of launch
+    q.both(TD_KERNEL_LARGE);
+    q.expect("td_set_step_kernel(large)", 0, 0, 1, 1);
+    q.format(F16);
+    q.expect("forced large, then float16", 0, 0, 1, 1);
+    q.format(F32);
+    q.expect("forced large, float32 again", 0, 0, 1, 1);
+    // TD_KERNEL_AUTO gives both back to their rules, in the format of the moment
+    q.both(TD_KERNEL_AUTO);
+    q.expect("td_set_step_kernel(auto)", 2, 1, 0, 0);
+    q.format(F16);
+    q.expect("auto, then float16", 1, 1, 0, 0);
+    q.format(F32);
+    q.expect("auto, float32 again", 2, 1, 0, 0);
+    // the retained setter leaves the full kind alone, forced or not
+    q.retained(TD_KERNEL_SMALL2);
+    q.expect("td_set_retained_step_kernel(small2)", 2, 2, 0, 1);
+    q.format(F16);
+    q.expect("retained small2 survives float16; the full kind follows its rule", 1, 2, 0, 1);
+    q.format(F32);
+    q.retained(TD_KERNEL_LARGE);
+    q.expect("td_set_retained_step_kernel(large)", 2, 0, 0, 1);
+    q.retained(TD_KERNEL_AUTO);
+    q.expect("td_set_retained_step_kernel(auto)", 2, 1, 0, 0);
+    q.both(TD_KERNEL_SMALL);
+    q.retained(TD_KERNEL_SMALL2);
+    q.expect("full forced small, retained forced small2", 1, 2, 1, 1);
+    q.retained(TD_KERNEL_AUTO);
+    q.expect("retained back to its rule on a forced full kind: the full kind stays forced", 1, 1, 1, 0);
+    q.both(TD_KERNEL_LARGE);
+    q.retained(TD_KERNEL_AUTO);
+    q.expect("the rule on a forced large kind", 0, 1, 1, 0);
+    q.both(TD_KERNEL_AUTO);
+    q.expect("td_set_step_kernel(auto) takes a forced retained kind back too", 2, 1, 0, 0);
+  }
+  // the kind / map-side check, with the caller's name; an unknown kind wins over the map side
+  for (const char* fn : {"td_set_step_kernel", "td_set_retained_step_kernel"}) {
+    char want[200];
+    for (int L : {10, 20, 30, 12})
+      for (int kind : {0, 1}) expect_kind_ok(fn, kind, L, "");
+    for (int L : {10, 20, 30})
+      for (int kind : {2, 3}) expect_kind_ok(fn, kind, L, "");
+    for (int L : {4, 12, 32})
+      for (int kind : {2, 3}) {
+        std::snprintf(want, sizeof want, "%s: L = %d has no small-batch step kernel (only L = 10 / 20 / 30)", fn, L);
+        expect_kind_ok(fn, kind, L, want);
+      }
+    for (int L : {10, 12})
+      for (int kind : {-1, 4, -2147483647 - 1}) {
+        std::snprintf(want, sizeof want, "%s: unknown kernel kind %d", fn, kind);
+        expect_kind_ok(fn, kind, L, want);
+      }
+  }
   if (g_bad) return 1;
   std::printf("retained_kernel: %d cases ok\n", g_cases);
   return 0;

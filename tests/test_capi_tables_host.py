@@ -1,8 +1,8 @@
 """The host logic td_capi.hip keeps in plain headers -- the export / import record
-(td_state_rec.h), the TD_KERNEL_AUTO and write-through rules (td_kernel_choice.h) and the
-retained-observation ledger (td_obs_ledger.h) -- run as stand-alone host programs under the
-address and undefined-behaviour sanitizers, and the Python mirror of the record's layout held to
-the C table -- all without a GPU."""
+(td_state_rec.h), the TD_KERNEL_AUTO and write-through rules (td_kernel_choice.h), the
+retained-observation ledger (td_obs_ledger.h) and the list calls' refusals (td_call_check.h) -- run
+as stand-alone host programs under the address and undefined-behaviour sanitizers, and the Python
+mirror of the record's layout held to the C table -- all without a GPU."""
 import os
 import re
 import shutil
@@ -74,6 +74,14 @@ def test_kernel_choice_table(cxx, tmp_path):
     (float32 and float16, L = 10 / 20 / 30 and a generic L), and the write-through rule on both
     sides of 192 MiB."""
     _run(cxx, tmp_path, "kernel_choice")
+
+
+def test_call_check_refusals(cxx, tmp_path):
+    """scripts/call_check_host.cpp: what a partial step refuses of the handle's settings (frame skip
+    before random_agent = 0 with auto-reset) and a device-list call of its cap and pointers (cap < 0,
+    cap > B, an empty list, a NULL list, in that order), each with its whole message and the
+    caller's name (td_call_check.h)."""
+    _run(cxx, tmp_path, "call_check")
 
 
 def test_obs_ledger_contract(cxx, tmp_path):

@@ -1,5 +1,5 @@
 """The kernel of a skipping launch without a GPU: the rule and the resolution order of a
-handle's two kinds (td_kernel_choice.h retained_kernel_kind, resolve_step_kinds) run as a
+handle's two kinds (td_kernel_choice.h retained_kernel_kind, KernelChoice::resolve) run as a
 stand-alone host program under the address and undefined-behaviour sanitizers, and the two new
 functions as the headers declare them and the ctypes binding binds them."""
 import ctypes
