@@ -1,5 +1,5 @@
 // td_call_check.h -- what the list calls refuse of the handle's settings and of a device list's
-// arguments, each written once.  Plain C++, no HIP: functions of the handle's ints that write a
+// arguments, and the sampler of its io, each written once.  Plain C++, no HIP: functions of the handle's ints that write a
 // message and take the caller's name; td_capi.hip calls them before anything is enqueued, and
 // scripts/call_check_host.cpp runs them alone.  (The contents of a host list: td_ids_check.h,
 // td_copy_check.h; of a device list: the check kernel, td_list_check.h.)
@@ -34,6 +34,35 @@ inline int list_args_check(const char* fn, int cap, int B, bool have_lists, cons
   else if (!have_lists) std::snprintf(msg, n, "%s: %s is NULL with cap = %d", fn, lists, cap);
   else return LIST_ARGS_GO;
   return LIST_ARGS_REFUSED;
+}
+
+// What td_sample_actions and its list forms refuse of their io, in this order: a NULL io, a bad
+// size / abi word, a NULL handle, no action output wanted, an output or count for a side the
+// mode lacks.  The caller fills in the pointers' presence only once the two header words match
+// (a struct of another layout is not read past them).  mode: 0 TD-def, 1 TD-atk, 2 TD-2p.
+struct SampleIoSeen {
+  bool io = false;                // io != NULL
+  unsigned size = 0, abi = 0;     // its two header words
+  bool handle = false;            // h != NULL
+  int mode = 0;                   // the handle's
+  bool def_act = false, atk_act = false, def_count = false, atk_count = false;  // != NULL
+};
+inline bool sample_io_header_ok(const SampleIoSeen& v, unsigned want_size, int want_abi) {
+  return v.io && v.size == want_size && v.abi == (unsigned)want_abi;
+}
+inline bool sample_io_refused(const char* fn, const SampleIoSeen& v, unsigned want_size, int want_abi, char* msg, size_t n) {
+  if (!v.io) std::snprintf(msg, n, "%s: NULL io", fn);
+  else if (!sample_io_header_ok(v, want_size, want_abi))
+    std::snprintf(msg, n, "%s: td_sample_io has size %u / abi %u, this library expects size %u / abi %d "
+                  "(call td_sample_io_init)", fn, v.size, v.abi, want_size, want_abi);
+  else if (!v.handle) std::snprintf(msg, n, "%s: NULL handle", fn);
+  else if (!v.def_act && !v.atk_act) std::snprintf(msg, n, "%s: no action output wanted (def_act and atk_act are NULL)", fn);
+  else if ((v.def_act || v.def_count) && v.mode == 1)
+    std::snprintf(msg, n, "%s: TD-atk has no defender side (def_act / def_count)", fn);
+  else if ((v.atk_act || v.atk_count) && v.mode == 0)
+    std::snprintf(msg, n, "%s: TD-def has no attacker side (atk_act / atk_count)", fn);
+  else return false;
+  return true;
 }
 
 }  // namespace td

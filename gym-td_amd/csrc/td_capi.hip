@@ -31,6 +31,7 @@
 #include "td_layout.h"
 #include "td_obs_ledger.h"
 #include "td_rng.h"
+#include "td_sample.h"
 #include "td_state_rec.h"
 #include "td_step_launch.h"
 
@@ -88,7 +89,7 @@ constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw doe
 constexpr int kIdSlots = 4;      // td_copy_boards, td_step_boards: id uploads in flight before a call waits for the oldest
 // The strings the kernel-name accessors hand out: one slot each, so a name stays valid until
 // its own accessor is called again (kept_name).
-enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SLOTS };
+enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_SLOTS };
 
 }  // namespace
 
@@ -99,7 +100,7 @@ struct td_handle {
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
-  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name
+  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -527,7 +528,7 @@ int create_setup(td_handle* h) {
   return td_seed(h, seeds.data(), seeds.data());
 }
 
-// td_step_io_init, td_mask_io_init: all zero but the two header words.
+// td_step_io_init, td_mask_io_init, td_sample_io_init: all zero but the two header words.
 template <class IO>
 void io_init(IO* io) {
   if (!io) return;
@@ -1198,6 +1199,83 @@ const char* td_action_mask_boards_kernel_name(td_handle* h) {
   char buf[64];
   std::snprintf(buf, sizeof buf, "td_mask_list_kernel<%d>", with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
   return kept_name(h, NAME_MASK_LIST, buf);
+}
+
+void td_sample_io_init(td_sample_io* io) { io_init(io); }
+
+namespace {
+
+// What td_sample_actions and its list forms check of their io (td_call_check.h
+// sample_io_refused), and the kernel arguments they make of it.  fn: the caller's name.
+int check_sample_io(const char* fn, const td_handle* h, const td_sample_io* io, SampleArgs* out) {
+  SampleIoSeen v;
+  v.io = io != nullptr;
+  if (io) { v.size = io->size; v.abi = io->abi; }
+  v.handle = h != nullptr;
+  if (sample_io_header_ok(v, (unsigned)sizeof(td_sample_io), TD_ABI_VERSION) && h) {
+    v.mode = h->mode;
+    v.def_act = io->def_act; v.atk_act = io->atk_act; v.def_count = io->def_count; v.atk_count = io->atk_count;
+  }
+  char msg[240];
+  if (sample_io_refused(fn, v, (unsigned)sizeof(td_sample_io), TD_ABI_VERSION, msg, sizeof msg)) return fail("%s", msg);
+  SampleArgs& a = *out;
+  std::memset(&a, 0, sizeof a);
+  a.B = h->B; a.L = h->L; a.multi = h->multi; a.xcd_map = h->xcd_map;
+  a.hdr = h->d_hdr; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.cfg = h->d_cfg + h->epoch;
+  a.def_act = io->def_act; a.atk_act = io->atk_act; a.def_count = io->def_count; a.atk_count = io->atk_count;
+  a.key = sample_key(io->seed, io->ticket);
+  a.def_idle = io->def_idle; a.atk_idle = io->atk_idle;
+  return 0;
+}
+
+}  // namespace
+
+// One kernel on the caller's stream; nothing is waited for.  Like the masks the calls only read
+// state: no launch for the refill cadence or the ring guard, no timing pair, the observation
+// ledger left alone.
+int td_sample_actions(td_handle* h, const td_sample_io* io, void* stream) {
+  SampleArgs a;
+  if (check_sample_io("td_sample_actions", h, io, &a)) return -1;
+  HIP_OK(launch_sample(a, nullptr, h->B, nullptr, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+// The boards named, every other row left as it is: td_action_mask_boards' path (ids_check, the
+// pinned id slots and d_pairs).
+int td_sample_actions_boards(td_handle* h, const td_sample_io* io, const int32_t* boards, int n, void* stream) {
+  SampleArgs a;
+  if (check_sample_io("td_sample_actions_boards", h, io, &a)) return -1;
+  char msg[200];
+  if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("td_sample_actions_boards: %s", msg);
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (upload_ids(h, boards, nullptr, n, s)) return -1;
+  HIP_OK(launch_sample(a, h->d_pairs, n, nullptr, nullptr, s));
+  return 0;
+}
+
+// The same for a device list: td_action_mask_boards_dev's path (the check kernel in front, the
+// call takes the next serial; a refused list writes no output byte).
+int td_sample_actions_boards_dev(td_handle* h, const td_sample_io* io, const int32_t* boards_dev, int cap,
+                                 const int32_t* count_dev, td_list_status* status_dev, void* stream) {
+  const char* fn = "td_sample_actions_boards_dev";
+  // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
+  if (io && io->size == (uint32_t)sizeof(td_sample_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
+    return check_list_args(fn, cap, 0, false, "");
+  SampleArgs a;
+  if (check_sample_io(fn, h, io, &a)) return -1;
+  if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
+  hipStream_t s = (hipStream_t)stream;
+  if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
+  HIP_OK(launch_sample(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
+  return 0;
+}
+
+const char* td_sample_actions_kernel_name(td_handle* h) {
+  if (!h) return "";
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "td_sample_kernel<%d>", with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
+  return kept_name(h, NAME_SAMPLE, buf);
 }
 
 // Both kernel-kind setters: the kind is checked against the map side (td_kernel_choice.h

@@ -181,6 +181,29 @@ static_assert(kMaskListWaves >= 1 && kMaskListWaves <= 8, "waves of one workgrou
 hipError_t launch_mask_list(const MaskArgs& a, const int32_t* ids, int cap, const int32_t* count,
                             const td_list_status* verdict, hipStream_t s);
 
+// One uniformly drawn legal action per side and board (td_sample_actions[_boards[_dev]];
+// td_sample.hip): reads what the mask kernels read, writes only the outputs.
+struct SampleArgs {
+  int B, L, multi;
+  int xcd_map;           // as MaskArgs
+  const TdHdr* hdr;
+  const uint32_t* tw_inf;
+  const uint32_t* cells;
+  const TdDevCfg* cfg;   // the current constant block
+  int64_t* def_act;      // [B] or [B][6][L][L], or nullptr
+  int64_t* atk_act;      // [B][3][8] or nullptr
+  int32_t* def_count;    // [B] or nullptr
+  int32_t* atk_count;    // [B] or nullptr
+  uint64_t key;          // sample_key(seed, ticket) (td_sample.h)
+  uint32_t def_idle, atk_idle;
+};
+constexpr int kSampleWaves = 4;  // entries (waves) per workgroup, as kMaskListWaves
+// ids == nullptr: every board (cap = B, entry i is board i); else td_mask_list_kernel's contract:
+// boards ids[0 .. cap) where verdict == nullptr, else ids[0 .. *count) unless the check kernel
+// launched in front refused the list.  One wave per entry of cap >= 1.
+hipError_t launch_sample(const SampleArgs& a, const int32_t* ids, int cap, const int32_t* count,
+                         const td_list_status* verdict, hipStream_t s);
+
 // Staged layouts per board: sixteen episodes of slack for the side refills, and the
 // ring guard (td_refill_kernel) needs to run only every NSLOT - 1 steps.  (NSLOT = 4 with
 // a guard every 3rd step: +4 % / +7-9 % per step at 8,192 / 4,096 boards, profiles/r03/s13.)

@@ -75,6 +75,19 @@ class TdMaskIO(ctypes.Structure):
         super().__init__(**kw)
 
 
+class TdSampleIO(ctypes.Structure):
+    """struct td_sample_io (tdstep.h): the size / ABI header, the device outputs, seed and ticket,
+    the idle probabilities in units of 2^-32."""
+    _fields_ = [("size", ctypes.c_uint32), ("abi", ctypes.c_uint32), ("def_act", c_vp), ("atk_act", c_vp),
+                ("def_count", c_vp), ("atk_count", c_vp), ("seed", ctypes.c_uint64), ("ticket", ctypes.c_uint64),
+                ("def_idle", ctypes.c_uint32), ("atk_idle", ctypes.c_uint32)]
+
+    def __init__(self, **kw):
+        kw.setdefault("size", ctypes.sizeof(TdSampleIO))
+        kw.setdefault("abi", ABI_VERSION)
+        super().__init__(**kw)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("libtdstep.so not found at %s -- build it with `make -C gym-td_amd/csrc` "
@@ -115,6 +128,12 @@ def _load():
         "td_action_mask_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdMaskIO), c_vp, ctypes.c_int, c_vp, c_vp,
                                                      c_vp]),
         "td_action_mask_boards_kernel_name": (ctypes.c_char_p, [c_vp]),
+        "td_sample_io_init": (None, [ctypes.POINTER(TdSampleIO)]),
+        "td_sample_actions": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleIO), c_vp]),
+        "td_sample_actions_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleIO), c_vp, ctypes.c_int, c_vp]),
+        "td_sample_actions_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleIO), c_vp, ctypes.c_int, c_vp, c_vp,
+                                                        c_vp]),
+        "td_sample_actions_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
         "td_layout_from_roads": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_u32p]),
         "td_layout_generate": (ctypes.c_int, [c_u32p, ctypes.c_int, ctypes.c_int, c_u32p]),

@@ -14,6 +14,7 @@ import torch
 
 from . import _lib
 from . import params as P
+from . import sampling
 
 MODES = {"def": 0, "atk": 1, "2p": 2}
 
@@ -166,12 +167,19 @@ class TDEngine(object):
           launch that writes one observation; reward is the sum, done / info those of the
           last board step run (a board stops at its episode's end), RealAction / FailCode
           those of the first.  Discrete actions and random_agent=True only.
+    sample_seed: the seed of ``sample_actions`` (an int in [0, 2**64), default 0): its draws
+          are a function of this seed, the call's ticket and the board id, and of nothing else.
     """
 
     def __init__(self, map_size, n_boards, mode="def", multi_action=None, difficulty=1, device=None,
                  np_seeds=None, py_seeds=None, autoreset=True, info=True, cfg=None, hp=None, host_io=False,
-                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32, retain_obs=True, frame_skip=1):
+                 random_agent=True, step_kernel="auto", obs_dtype=torch.float32, retain_obs=True, frame_skip=1,
+                 sample_seed=0):
         frame_skip = _check_frame_skip(frame_skip)  # (before td_create: no device is touched)
+        if isinstance(sample_seed, (bool, np.bool_)) or not isinstance(sample_seed, (int, np.integer)) or \
+                not 0 <= int(sample_seed) <= sampling.M64:
+            raise ValueError("sample_seed must be an int in [0, 2**64), not %r" % (sample_seed,))
+        self.sample_seed, self._sample_ticket = int(sample_seed), 0
         # state serial: advanced by every call that can change a board or the config (_changed);
         # _mask_at: the serial at which the mask / code buffers were last written whole
         self._state_serial, self._mask_at, self._mask_pending = 0, {}, None
@@ -651,6 +659,93 @@ class TDEngine(object):
         """The kernel ``action_mask_boards`` and ``action_mask_boards_dev`` launch
         (td_action_mask_boards_kernel_name), e.g. 'td_mask_list_kernel<10>'."""
         return _lib.lib.td_action_mask_boards_kernel_name(self._h).decode()
+
+    # ---------------------------------------------------------------- sampling
+    def _sample_prepare(self, ticket, def_idle, atk_idle, counts):
+        """The engine's sample buffers (allocated on first use: every row the no-op / all-4) as a
+        td_sample_io for this call's ticket."""
+        B, L = self.B, self.L
+        buf = getattr(self, "_sample_buf", None)
+        if buf is None:
+            buf = self._sample_buf = {"def": None, "atk": None, "def_count": None, "atk_count": None}
+            if self.mode != "atk":
+                if self.multi:
+                    buf["def"] = torch.zeros((B, 6, L, L), dtype=torch.int64, device=self.device)
+                else:
+                    buf["def"] = torch.full((B,), 6 * L * L, dtype=torch.int64, device=self.device)
+            if self.mode != "def":
+                buf["atk"] = torch.full((B, 3, 8), 4, dtype=torch.int64, device=self.device)
+        if counts:
+            for side in ("def", "atk"):
+                if buf[side] is not None and buf[side + "_count"] is None:
+                    buf[side + "_count"] = torch.zeros(B, dtype=torch.int32, device=self.device)
+        if ticket is None:
+            ticket = self._sample_ticket
+            self._sample_ticket = (ticket + 1) & sampling.M64
+        io = _lib.TdSampleIO(seed=self.sample_seed, ticket=int(ticket) & sampling.M64,
+                             def_idle=sampling.idle_units(def_idle), atk_idle=sampling.idle_units(atk_idle))
+        for name, key in (("def_act", "def"), ("atk_act", "atk"), ("def_count", "def_count"), ("atk_count", "atk_count")):
+            t = buf[key]
+            setattr(io, name, t.data_ptr() if t is not None and (counts or not key.endswith("count")) else None)
+        out = dict(buf)
+        if not counts:
+            out["def_count"] = out["atk_count"] = None
+        return io, out
+
+    def sample_actions(self, ticket=None, def_idle=0.0, atk_idle=0.0, counts=False):
+        """One uniformly drawn legal action per side and board, on the device
+        (td_sample_actions): what ``action_mask()`` + ``torch.multinomial`` would give, in one
+        kernel and in the formats ``step()`` takes.
+
+        Returns a dict of the engine's own device tensors (allocated on first use, overwritten
+        by the next call): ``"def"`` int64 (B,) -- the no-op 6 L^2 where nothing is legal or the
+        side idles -- or (B, 6, L, L) with multi-action (one flag at most), ``"atk"`` int64
+        (B, 3, 8), all 4 but the chosen road's first slot, and with ``counts`` ``"def_count"`` /
+        ``"atk_count"`` int32 (B,): the number of candidates (the pick's log-probability is
+        -log n).  A side the mode lacks, and the counts without ``counts``, are None.
+        ``def_idle`` / ``atk_idle``: the probability of choosing nothing although something is
+        legal, a float in [0, 1] (an int is taken in units of 2^-32).
+        The draw is a function of (``sample_seed``, ticket, board id) alone
+        (gym_TD.sampling.reference_sample): ``ticket=None`` uses and then advances the engine's
+        counter, an explicit ticket reproduces a call.  One candidate per side, so the step
+        executes what was sampled.  No board, stream or flag changes; one kernel on torch's
+        current stream, which must be the stream of step().  With ``host_io`` the tensors are
+        still on the device: copy them to the host for ``step()``."""
+        io, out = self._sample_prepare(ticket, def_idle, atk_idle, counts)
+        _lib.check(_lib.lib.td_sample_actions(self._h, io, self._stream()))
+        return out
+
+    def sample_actions_boards(self, boards, ticket=None, def_idle=0.0, atk_idle=0.0, counts=False):
+        """``sample_actions`` for the boards named in ``boards`` only (td_sample_actions_boards),
+        the partner of ``step_boards``: the tensors keep their full-batch shape, only the named
+        rows are written, and a named board's row is the one ``sample_actions`` gives it under
+        the same ticket.  ``boards`` under ``step_boards``' rules; TDError, nothing written: an
+        id out of range or named twice.  ``frame_skip`` > 1 and random_agent=False are fine."""
+        ids = _board_ids(boards)
+        io, out = self._sample_prepare(ticket, def_idle, atk_idle, counts)
+        _lib.check(_lib.lib.td_sample_actions_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
+        return out
+
+    def sample_actions_boards_dev(self, boards, count=None, status=None, ticket=None, def_idle=0.0, atk_idle=0.0,
+                                  counts=False):
+        """``sample_actions_boards`` for ids that are on the device (td_sample_actions_boards_dev),
+        the partner of ``step_boards_dev``: nothing is copied to the host or waited for.
+        ``boards``, ``count`` and ``status`` as in ``step_boards_dev``; a list the device refuses
+        writes no byte (``list_errors()``).  The tensors stay alive until the next call."""
+        ids = _dev_ids(boards, self.device, "sample_actions_boards")
+        c = _dev_words(count, 1, self.device, "count")
+        st = _dev_words(status, 4, self.device, "status")
+        io, out = self._sample_prepare(ticket, def_idle, atk_idle, counts)
+        _lib.check(_lib.lib.td_sample_actions_boards_dev(self._h, io, ids.data_ptr(), int(ids.numel()),
+                                                         c.data_ptr() if c is not None else None,
+                                                         st.data_ptr() if st is not None else None, self._stream()))
+        self._keep_sample_list = (ids, c, st)  # alive until the next call's kernels are behind them on the stream
+        return out
+
+    def sample_actions_kernel_name(self):
+        """The kernel the three sampling calls launch (td_sample_actions_kernel_name), e.g.
+        'td_sample_kernel<10>'."""
+        return _lib.lib.td_sample_actions_kernel_name(self._h).decode()
 
     def _changed(self, rows=None):
         """Called in front of every call that can change a board or the config: the state

@@ -329,18 +329,20 @@ class TDVecEnv(object):
     ``obs_dtype=torch.float16``: the observation as float16 (TDEngine's ``obs_dtype``).
     ``frame_skip=k``: every step() is a macro step of k board steps (TDEngine's
     ``frame_skip``); with ``action_mask=True`` the mask describes the state it left.
+    ``sample_seed``: the seed of ``sample_actions()`` (TDEngine's ``sample_seed``).
     """
 
     def __init__(self, map_size, num_envs, mode="def", difficulty=1, multi_action=None, seed=0, global_offset=0,
                  device=None, info=True, autoreset=True, host_io=False, random_agent=True, action_mask=False,
-                 obs_dtype=torch.float32, frame_skip=1):
+                 obs_dtype=torch.float32, frame_skip=1, sample_seed=0):
         self.map_size, self.num_envs, self.mode = int(map_size), int(num_envs), mode
         self.with_action_mask = bool(action_mask)
         self._masks = None
         seeds = np.arange(num_envs, dtype=np.int64) + int(seed) + int(global_offset)
         self.engine = TDEngine(map_size, num_envs, mode, multi_action, difficulty, device=device,
                                np_seeds=seeds, py_seeds=seeds, autoreset=autoreset, info=info, host_io=host_io,
-                               random_agent=random_agent, obs_dtype=obs_dtype, frame_skip=frame_skip)
+                               random_agent=random_agent, obs_dtype=obs_dtype, frame_skip=frame_skip,
+                               sample_seed=sample_seed)
         self.frame_skip = self.engine.frame_skip
         L = self.map_size
         self.observation_space = Box(low=0., high=1., shape=(45, L, L),
@@ -408,6 +410,33 @@ class TDVecEnv(object):
         by the same device list."""
         return self._step(actions, lambda **kw: self.engine.step_boards_dev(boards, count=count, status=status, **kw),
                           partial=True)
+
+    def _sampled(self, out):
+        """A sampling call's dict as the actions step() takes for the mode."""
+        if self.mode == "def":
+            return out["def"]
+        if self.mode == "atk":
+            return out["atk"]
+        return {"Attacker": out["atk"], "Defender": out["def"]}
+
+    def sample_actions(self, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """One uniformly drawn legal action per env, on the device (TDEngine.sample_actions),
+        as step() takes it for the mode: the defender's tensor, the attacker's, or the dict of
+        both in TD-2p.  Needs neither ``action_mask=True`` nor the mask buffers; the tensors are
+        the engine's own, overwritten by the next sampling call."""
+        return self._sampled(self.engine.sample_actions(ticket, def_idle, atk_idle))
+
+    def sample_actions_boards(self, boards, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """sample_actions() for the envs named in ``boards`` only
+        (TDEngine.sample_actions_boards), the partner of step_boards(): full-batch tensors,
+        the named rows fresh."""
+        return self._sampled(self.engine.sample_actions_boards(boards, ticket, def_idle, atk_idle))
+
+    def sample_actions_boards_dev(self, boards, count=None, status=None, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """sample_actions_boards() for env ids that are on the device
+        (TDEngine.sample_actions_boards_dev), the partner of step_boards_dev(): with fork_dev() a
+        search iteration -- fork, sample, step -- without a host round trip."""
+        return self._sampled(self.engine.sample_actions_boards_dev(boards, count, status, ticket, def_idle, atk_idle))
 
     def _step(self, actions, run, partial=False):
         if self.mode == "def":

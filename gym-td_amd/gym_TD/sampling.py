@@ -1,0 +1,77 @@
+"""Uniform legal-action sampling restated in numpy: the reference of ``TDEngine.sample_actions``.
+
+The rule of csrc/td_sample.h -- splitmix64 over (seed, ticket, board id, draw), an idle draw and
+a multiply-shift pick per side -- applied to the masks of ``gym_TD.masks.reference_masks``.
+"""
+import numpy as np
+
+M64 = (1 << 64) - 1
+DEF_IDLE, DEF_PICK, ATK_IDLE, ATK_PICK = range(4)  # the draw j
+
+
+def sm(z):
+    """splitmix64's output step on z + 0x9E3779B97F4A7C15 (mod 2^64)."""
+    z = (z + 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def word(seed, ticket, b, j):
+    """The 64-bit word of draw j of board b under (seed, ticket)."""
+    return sm((sm((sm(int(seed) & M64) + int(ticket)) & M64) + 4 * int(b) + int(j)) & M64)
+
+
+def u32(seed, ticket, b, j):
+    return word(seed, ticket, b, j) >> 32
+
+
+def idle_units(p):
+    """An idle probability as the call takes it: an int is units of 2^-32, a float a probability."""
+    if isinstance(p, (int, np.integer)) and not isinstance(p, (bool, np.bool_)):
+        if not 0 <= int(p) <= 0xFFFFFFFF:
+            raise ValueError("idle probability in units of 2^-32 must be in [0, 2^32), not %r" % (p,))
+        return int(p)
+    p = float(p)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("idle probability must be in [0, 1], not %r" % (p,))
+    return min(2 ** 32 - 1, int(p * 2 ** 32))
+
+
+def _choose(cand, seed, ticket, b, j_idle, j_pick, idle):
+    """The chosen candidate, or None: nothing is legal, or the idle draw fires."""
+    n = len(cand)
+    if n == 0 or u32(seed, ticket, b, j_idle) < idle:
+        return None
+    return int(cand[(u32(seed, ticket, b, j_pick) * n) >> 32])
+
+
+def reference_sample(def_mask, atk_mask, seed, ticket, b, def_idle, atk_idle, L, multi):
+    """(def_act, atk_act, def_count, atk_count) of board b, in the step's formats.
+
+    def_mask: reference_masks' row, (6 L^2 + 1,) or (6, L, L) with ``multi``, or None (TD-atk);
+    atk_mask: (3, 5) or None (TD-def).  def_idle / atk_idle: units of 2^-32 (ints) or
+    probabilities (floats).  def_act: int (6 L^2 = the no-op) or int64 (6, L, L) with one flag
+    at most; atk_act: int64 (3, 8), all 4 but the chosen road's first slot.  A side without a
+    mask gives None for its action and its count.
+    """
+    A = 6 * L * L
+    d_act = a_act = d_n = a_n = None
+    if def_mask is not None:
+        cand = np.flatnonzero(np.asarray(def_mask).reshape(-1)[:A])
+        d_n = len(cand)
+        k = _choose(cand, seed, ticket, b, DEF_IDLE, DEF_PICK, idle_units(def_idle))
+        if multi:
+            d_act = np.zeros((6, L, L), dtype=np.int64)
+            if k is not None:
+                d_act.reshape(-1)[k] = 1
+        else:
+            d_act = A if k is None else k
+    if atk_mask is not None:
+        cand = np.flatnonzero(np.asarray(atk_mask)[:, :4].reshape(-1))  # road * 4 + t
+        a_n = len(cand)
+        k = _choose(cand, seed, ticket, b, ATK_IDLE, ATK_PICK, idle_units(atk_idle))
+        a_act = np.full((3, 8), 4, dtype=np.int64)
+        if k is not None:
+            a_act[k // 4, 0] = k % 4
+    return d_act, a_act, d_n, a_n

@@ -555,6 +555,70 @@ int td_action_mask_boards_dev(td_handle* h, const td_mask_io* io, const int32_t*
  * generic side).  The string is the handle's, valid until the next call. */
 const char* td_action_mask_boards_kernel_name(td_handle* h);
 
+/* One uniformly drawn legal action per side and board, on the device: what a random-legal
+ * baseline, the default policy of a rollout or the exploring branch of an epsilon-greedy trainer
+ * would otherwise make of td_action_mask's rows on their own.  The candidates are the entries
+ * td_action_mask would mark 1, the always-legal ones aside:
+ *   defender, discrete      a in [0, 6 L^2) with def_mask[a] == 1, in ascending a; n_def of them
+ *                           (0 while the cool-down is closed and on a board never reset).  The
+ *                           action is 6 L^2 (the no-op) if n_def == 0 or the idle draw fires,
+ *                           else the k-th candidate.
+ *   defender, multi-action  the legal flags of [6][L][L] in flat order; the output row is written
+ *                           whole: zeros, and a single 1 at the chosen flag where one is chosen.
+ *   attacker                the pairs (road, t < 4) with atk_mask[road][t] == 1 in ascending
+ *                           road * 4 + t; the output [3][8] is all 4, and [road][0] = t where a
+ *                           pair is chosen.
+ * One candidate per side and call, so the step executes what was sampled: RealAction is the
+ * sampled action and FailCode 0 (several flags at once interact: out of scope, as for the mask).
+ * The randomness is stateless -- splitmix64 over (seed, ticket, board id, draw):
+ *   sm(z): z += 0x9E3779B97F4A7C15; z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *          z *= 0x94D049BB133111EB; z ^= z >> 31
+ *   word(seed, ticket, b, j) = sm(sm(sm(seed) + ticket) + 4 b + j),  u = word >> 32
+ *   j = 0: the defender idles iff u < def_idle;  j = 1: its pick k = (u * n_def) >> 32
+ *   j = 2: the attacker idles iff u < atk_idle;  j = 3: its pick k = (u * n_atk) >> 32
+ * (bias of the pick <= n / 2^32, n <= 6,144; no rejection loop).  A call writes nothing but its
+ * outputs -- no board, RNG stream, flag, ledger or refill cadence changes --, is reproducible,
+ * and two copies of one board at different ids draw differently: vary `ticket` per call.
+ *   def_act    int64, td_step_io.def_act's format ([B] or [B][6][L][L]); NULL = not wanted
+ *   atk_act    int64 [B][3][8]; NULL = not wanted
+ *   def_count  int32 [B] n_def, atk_count int32 [B] n_atk; may be NULL (the log-probability of a
+ *              pick is -log n)
+ *   def_idle, atk_idle  probability of choosing nothing although something is legal, in units
+ *              of 2^-32; 0 = only when nothing is legal
+ * Refused (< 0, nothing launched), in this order: a NULL io, a bad size / abi word, a NULL
+ * handle, no action output wanted (def_act and atk_act both NULL), an output or count for a side
+ * the mode lacks.  Asynchronous on `stream`, which must be the step's stream; nothing is waited
+ * for.  The calls take no td_kernel_timing pair and are no launch for the refill cadence.
+ * td_sample_actions_boards / _boards_dev -- the list forms, under td_action_mask_boards[_dev]'s
+ *   contract word for word: the arrays keep their full-batch shape and are indexed by board id
+ *   (the layout td_step_boards reads), only the named rows are written, and the row of a named
+ *   board is the row td_sample_actions gives that board under the same seed and ticket (the key
+ *   is the board id, not the list position).  Host list: n < 0 or n > the handle's boards, NULL
+ *   boards with n > 0, an id out of range or named twice are refused on the host; n == 0
+ *   returns 0.  Device list: cap < 0 (with the io words, before the handle), cap > the handle's
+ *   boards and NULL boards_dev on the host; TD_LIST_BAD_COUNT, TD_LIST_RANGE, TD_LIST_TWICE on
+ *   the device (td_list_check_kernel in front, the next serial of the handle's device-list
+ *   calls): then no output byte is written, the call returned 0 and td_list_errors counts it.
+ *   td_frame_skip() > 1 and random_agent = 0 are no reason to refuse. */
+typedef struct td_sample_io {
+  uint32_t size, abi;          /* checked first, as td_step_io / td_mask_io */
+  int64_t* def_act;
+  int64_t* atk_act;
+  int32_t* def_count;
+  int32_t* atk_count;
+  uint64_t seed, ticket;
+  uint32_t def_idle, atk_idle;
+} td_sample_io;
+/* Zero *io and set its size / abi words. */
+void td_sample_io_init(td_sample_io* io);
+int td_sample_actions(td_handle* h, const td_sample_io* io, void* stream);
+int td_sample_actions_boards(td_handle* h, const td_sample_io* io, const int32_t* boards, int n, void* stream);
+int td_sample_actions_boards_dev(td_handle* h, const td_sample_io* io, const int32_t* boards_dev, int cap,
+                                 const int32_t* count_dev, td_list_status* status_dev, void* stream);
+/* The kernel the three calls launch, as rocprofv3 shows it: "td_sample_kernel<10>" (L, or 0 for
+ * a generic side).  The string is the handle's, valid until the next call. */
+const char* td_sample_actions_kernel_name(td_handle* h);
+
 /* Which step kernel td_step launches (one wave per board in all three; they differ in
  * occupancy and load schedule, not in results):
  *   TD_KERNEL_LARGE  td_step_kernel        several rounds of waves (7 per SIMD), live slots
