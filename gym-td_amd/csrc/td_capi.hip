@@ -470,6 +470,69 @@ int enqueue_list_check(td_handle* h, const int32_t* src, const int32_t* dst, int
   return 0;
 }
 
+// A device list's cap and pointers against B boards (td_call_check.h list_args_check): 1 go on,
+// 0 an empty list (the call returns 0), -1 refused.  B = 0 where a call has no handle yet: cap < 0.
+int check_list_args(const char* fn, int cap, int B, bool have_lists, const char* lists) {
+  char msg[200];
+  const int go = list_args_check(fn, cap, B, have_lists, lists, msg, sizeof msg);
+  return go == LIST_ARGS_REFUSED ? fail("%s", msg) : go;
+}
+
+// cap < 0 needs no handle: a device-list call with an io refuses it once the io's two header
+// words match, in front of the handle's checks.  True: refused.
+template <class Io>
+bool negative_cap_refused(const char* fn, const Io* io, int cap) {
+  return io && io->size == (uint32_t)sizeof(Io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0 &&
+         check_list_args(fn, cap, 0, false, "") < 0;
+}
+
+// What the mask and sample kernels read of the handle's boards.
+BoardView board_view(const td_handle* h) {
+  return {h->B, h->L, h->multi, h->xcd_map, h->d_hdr, h->d_tw_inf, h->d_cells, h->d_cfg + h->epoch};
+}
+
+// The list forms of the calls that only read state (the masks, the sampler), each written once
+// over the call's io check and its list kernel's launch.  They are no launches for the refill
+// cadence or the ring guard, take no timing pair and leave the observation ledger alone.
+template <class Io, class Args>
+using IoCheck = int (*)(const char* fn, const td_handle* h, const Io* io, Args* out);
+template <class Args>
+using ListLaunch = hipError_t (*)(const Args& a, const int32_t* ids, int cap, const int32_t* count,
+                                  const td_list_status* verdict, hipStream_t s);
+
+// A host list.  Everything is checked here, before anything is enqueued; the ids reach the kernel
+// through the pinned id slots and d_pairs (upload_ids), as td_step_boards'.
+template <class Io, class Args>
+int read_boards(const char* fn, IoCheck<Io, Args> check, ListLaunch<Args> launch, td_handle* h, const Io* io,
+                const int32_t* boards, int n, void* stream) {
+  Args a;
+  if (check(fn, h, io, &a)) return -1;
+  char msg[200];
+  if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("%s: %s", fn, msg);
+  if (n == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (upload_ids(h, boards, nullptr, n, s)) return -1;
+  HIP_OK(launch(a, h->d_pairs, n, nullptr, nullptr, s));
+  return 0;
+}
+
+// A list, its length and its verdict in device memory, under td_step_boards_dev's contract: the
+// host checks what it can see, the check kernel the contents, on the stream in front of the list
+// kernel (the call takes the next serial); a refused list writes no output byte.
+template <class Io, class Args>
+int read_boards_dev(const char* fn, IoCheck<Io, Args> check, ListLaunch<Args> launch, td_handle* h, const Io* io,
+                    const int32_t* boards_dev, int cap, const int32_t* count_dev, td_list_status* status_dev,
+                    void* stream) {
+  if (negative_cap_refused(fn, io, cap)) return -1;
+  Args a;
+  if (check(fn, h, io, &a)) return -1;
+  if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
+  hipStream_t s = (hipStream_t)stream;
+  if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
+  HIP_OK(launch(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
+  return 0;
+}
+
 // td_create's memory: the device arrays, zeroed, and the pinned id slots with their events.
 int create_memory(td_handle* h) {
   const size_t B = (size_t)h->B;
@@ -972,14 +1035,6 @@ int check_partial_step(const char* fn, const td_handle* h, const td_step_io* io)
   return partial_step_refused(fn, h->frame_skip, h->opp_np, h->autoreset, msg, sizeof msg) ? fail("%s", msg) : 0;
 }
 
-// A device list's cap and pointers against B boards (td_call_check.h list_args_check): 1 go on,
-// 0 an empty list (the call returns 0), -1 refused.  B = 0 where a call has no handle yet: cap < 0.
-int check_list_args(const char* fn, int cap, int B, bool have_lists, const char* lists) {
-  char msg[200];
-  const int go = list_args_check(fn, cap, B, have_lists, lists, msg, sizeof msg);
-  return go == LIST_ARGS_REFUSED ? fail("%s", msg) : go;
-}
-
 }  // namespace
 
 int td_step(td_handle* h, const td_step_io* io, void* stream) {
@@ -1048,9 +1103,7 @@ int td_step_boards(td_handle* h, const td_step_io* io, const int32_t* boards, in
 int td_step_boards_dev(td_handle* h, const td_step_io* io, const int32_t* boards_dev, int cap, const int32_t* count_dev,
                        td_list_status* status_dev, void* stream) {
   const char* fn = "td_step_boards_dev";
-  // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
-  if (io && io->size == (uint32_t)sizeof(td_step_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
-    return check_list_args(fn, cap, 0, false, "");
+  if (negative_cap_refused(fn, io, cap)) return -1;
   if (check_partial_step(fn, h, io)) return -1;
   if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
   hipStream_t s = (hipStream_t)stream;
@@ -1143,10 +1196,7 @@ int check_mask_io(const char* fn, const td_handle* h, const td_mask_io* io, Mask
                   kMaskMaxPitch, h->L);
     pitch = io->def_pitch;
   }
-  MaskArgs& a = *out;
-  a.B = h->B; a.L = h->L; a.multi = h->multi; a.xcd_map = h->xcd_map;
-  a.hdr = h->d_hdr; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.cfg = h->d_cfg + h->epoch;
-  a.def_mask = io->def_mask; a.def_code = io->def_code; a.atk_mask = io->atk_mask; a.def_pitch = pitch;
+  *out = {board_view(h), io->def_mask, io->def_code, io->atk_mask, pitch};
   return 0;
 }
 
@@ -1160,38 +1210,15 @@ int td_action_mask(td_handle* h, const td_mask_io* io, void* stream) {
 }
 
 // td_action_mask for the boards named: the rows of every other board keep their bytes
-// (td_mask_list.hip).  Everything is checked here, before anything is enqueued; the ids reach
-// the kernel through the pinned id slots and d_pairs (upload_ids), as td_step_boards'.  The call
-// only reads state: it is no launch for the refill cadence or the ring guard, takes no timing
-// pair and leaves the observation ledger alone.
+// (td_mask_list.hip).
 int td_action_mask_boards(td_handle* h, const td_mask_io* io, const int32_t* boards, int n, void* stream) {
-  MaskArgs a;
-  if (check_mask_io("td_action_mask_boards", h, io, &a)) return -1;
-  char msg[200];
-  if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("td_action_mask_boards: %s", msg);
-  if (n == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (upload_ids(h, boards, nullptr, n, s)) return -1;
-  HIP_OK(launch_mask_list(a, h->d_pairs, n, nullptr, nullptr, s));
-  return 0;
+  return read_boards("td_action_mask_boards", check_mask_io, launch_mask_list, h, io, boards, n, stream);
 }
 
-// The same for a list, its length and its verdict in device memory, under td_step_boards_dev's
-// contract: the host checks what it can see, the check kernel the contents, on the stream in
-// front of the mask kernel; a refused list writes no output byte.
 int td_action_mask_boards_dev(td_handle* h, const td_mask_io* io, const int32_t* boards_dev, int cap,
                               const int32_t* count_dev, td_list_status* status_dev, void* stream) {
-  const char* fn = "td_action_mask_boards_dev";
-  // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
-  if (io && io->size == (uint32_t)sizeof(td_mask_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
-    return check_list_args(fn, cap, 0, false, "");
-  MaskArgs a;
-  if (check_mask_io(fn, h, io, &a)) return -1;
-  if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
-  hipStream_t s = (hipStream_t)stream;
-  if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
-  HIP_OK(launch_mask_list(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
-  return 0;
+  return read_boards_dev("td_action_mask_boards_dev", check_mask_io, launch_mask_list, h, io, boards_dev, cap, count_dev,
+                         status_dev, stream);
 }
 
 const char* td_action_mask_boards_kernel_name(td_handle* h) {
@@ -1218,13 +1245,8 @@ int check_sample_io(const char* fn, const td_handle* h, const td_sample_io* io, 
   }
   char msg[240];
   if (sample_io_refused(fn, v, (unsigned)sizeof(td_sample_io), TD_ABI_VERSION, msg, sizeof msg)) return fail("%s", msg);
-  SampleArgs& a = *out;
-  std::memset(&a, 0, sizeof a);
-  a.B = h->B; a.L = h->L; a.multi = h->multi; a.xcd_map = h->xcd_map;
-  a.hdr = h->d_hdr; a.tw_inf = h->d_tw_inf; a.cells = h->d_cells; a.cfg = h->d_cfg + h->epoch;
-  a.def_act = io->def_act; a.atk_act = io->atk_act; a.def_count = io->def_count; a.atk_count = io->atk_count;
-  a.key = sample_key(io->seed, io->ticket);
-  a.def_idle = io->def_idle; a.atk_idle = io->atk_idle;
+  *out = {board_view(h), io->def_act, io->atk_act, io->def_count, io->atk_count, sample_key(io->seed, io->ticket),
+          io->def_idle, io->atk_idle};
   return 0;
 }
 
@@ -1240,35 +1262,15 @@ int td_sample_actions(td_handle* h, const td_sample_io* io, void* stream) {
   return 0;
 }
 
-// The boards named, every other row left as it is: td_action_mask_boards' path (ids_check, the
-// pinned id slots and d_pairs).
+// The boards named, every other row left as it is.
 int td_sample_actions_boards(td_handle* h, const td_sample_io* io, const int32_t* boards, int n, void* stream) {
-  SampleArgs a;
-  if (check_sample_io("td_sample_actions_boards", h, io, &a)) return -1;
-  char msg[200];
-  if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("td_sample_actions_boards: %s", msg);
-  if (n == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (upload_ids(h, boards, nullptr, n, s)) return -1;
-  HIP_OK(launch_sample(a, h->d_pairs, n, nullptr, nullptr, s));
-  return 0;
+  return read_boards("td_sample_actions_boards", check_sample_io, launch_sample, h, io, boards, n, stream);
 }
 
-// The same for a device list: td_action_mask_boards_dev's path (the check kernel in front, the
-// call takes the next serial; a refused list writes no output byte).
 int td_sample_actions_boards_dev(td_handle* h, const td_sample_io* io, const int32_t* boards_dev, int cap,
                                  const int32_t* count_dev, td_list_status* status_dev, void* stream) {
-  const char* fn = "td_sample_actions_boards_dev";
-  // cap < 0 needs no handle: refused with the io words, in front of the handle's checks
-  if (io && io->size == (uint32_t)sizeof(td_sample_io) && io->abi == (uint32_t)TD_ABI_VERSION && cap < 0)
-    return check_list_args(fn, cap, 0, false, "");
-  SampleArgs a;
-  if (check_sample_io(fn, h, io, &a)) return -1;
-  if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
-  hipStream_t s = (hipStream_t)stream;
-  if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
-  HIP_OK(launch_sample(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
-  return 0;
+  return read_boards_dev("td_sample_actions_boards_dev", check_sample_io, launch_sample, h, io, boards_dev, cap, count_dev,
+                         status_dev, stream);
 }
 
 const char* td_sample_actions_kernel_name(td_handle* h) {

@@ -5,23 +5,19 @@
 // of no pairs: every wave exits before it reads an id or anything of any board.  A unit of its
 // own: see td_copy_body.h.
 #include "td_copy_body.h"
+#include "td_list_dev.h"
 
 namespace td {
 
-// src / dst: [cap] board ids; count: [1] or nullptr; verdict: the handle's record.  Count and
-// verdict were written by earlier kernels on the stream and by no wave of this one: wave-uniform
-// loads through the constant address space, as in td_step_list.h.  The check kernel refused a
-// count outside [0, cap], so n <= cap = the grid, and entries [0, n) were all validated.
+// src / dst: [cap] board ids; count: [1] or nullptr; verdict: the handle's record.  The pair
+// count is td_list_dev.h's dev_list_length: n <= cap = the grid, and entries [0, n) were all
+// validated.
 template <int LT>
 __global__ __launch_bounds__(64) void td_copy_list_kernel(StepArgs a, const int32_t* src, const int32_t* dst, int cap,
                                                           const int32_t* count, const td_list_status* verdict) {
   constexpr int NC = LT ? LT * LT : MAX_KERNEL_L * MAX_KERNEL_L;
   __shared__ Smem<NC> S;
-  typedef __attribute__((address_space(4))) const int32_t cword_t;
-  const int code = reinterpret_cast<cword_t*>(reinterpret_cast<uintptr_t>(verdict))[0];
-  int n = cap;
-  if (count) n = reinterpret_cast<cword_t*>(reinterpret_cast<uintptr_t>(count))[0];
-  n = code ? 0 : n;
+  const int n = dev_list_length(cap, count, verdict);
   TD_COPY_PAIR_BODY(src[i], dst[i])
 }
 

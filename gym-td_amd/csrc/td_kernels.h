@@ -1,7 +1,7 @@
 // td_kernels.h -- interface between the C-ABI (td_capi.hip) and the kernel units: the kernels'
 // arguments, the row lookups of the step, frame-skip and partial-step units (launched through
-// td_step_launch.h) and the launch_* functions of td_reset.hip, td_mask.hip, td_mask_list.hip and
-// td_copy.hip.
+// td_step_launch.h) and the launch_* functions of td_reset.hip, td_mask.hip, td_mask_list.hip,
+// td_sample.hip, td_copy.hip, td_copy_list.hip and td_list_check.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -150,16 +150,22 @@ hipError_t launch_copy_list(const StepArgs& a, const int32_t* src, const int32_t
 // The check of a device-resident list (td_list_check.hip): one thread per entry of a.cap >= 1.
 hipError_t launch_list_check(const ListCheckArgs& a, hipStream_t s);
 
-// Legal-action masks of the boards' present state (td_action_mask; td_mask.hip): which
-// action the next step would execute.  Reads the header, the cell words (map[6] in bits
-// 24-31), the tower words and the current constant block; writes only the outputs.
-struct MaskArgs {
+// What the mask and sample kernels read of the boards, filled from the handle in one place
+// (td_capi.hip board_view): the header, the cell words (map[6] in bits 24-31), the tower words
+// and the current constant block.  The first member of both kernels' arguments.
+struct BoardView {
   int B, L, multi;
   int xcd_map;           // block i serves board xcd_board(i, B) (else board i), as the step
   const TdHdr* hdr;
   const uint32_t* tw_inf;
   const uint32_t* cells;
   const TdDevCfg* cfg;   // the current constant block
+};
+
+// Legal-action masks of the boards' present state (td_action_mask; td_mask.hip): which
+// action the next step would execute.  Reads the view; writes only the outputs.
+struct MaskArgs {
+  BoardView v;
   uint8_t* def_mask;     // [B][def_pitch] or nullptr
   uint8_t* def_code;     // [B][def_pitch] or nullptr
   uint8_t* atk_mask;     // [B][3][5] or nullptr
@@ -182,14 +188,9 @@ hipError_t launch_mask_list(const MaskArgs& a, const int32_t* ids, int cap, cons
                             const td_list_status* verdict, hipStream_t s);
 
 // One uniformly drawn legal action per side and board (td_sample_actions[_boards[_dev]];
-// td_sample.hip): reads what the mask kernels read, writes only the outputs.
+// td_sample.hip): reads the view, writes only the outputs.
 struct SampleArgs {
-  int B, L, multi;
-  int xcd_map;           // as MaskArgs
-  const TdHdr* hdr;
-  const uint32_t* tw_inf;
-  const uint32_t* cells;
-  const TdDevCfg* cfg;   // the current constant block
+  BoardView v;
   int64_t* def_act;      // [B] or [B][6][L][L], or nullptr
   int64_t* atk_act;      // [B][3][8] or nullptr
   int32_t* def_count;    // [B] or nullptr
@@ -197,6 +198,14 @@ struct SampleArgs {
   uint64_t key;          // sample_key(seed, ticket) (td_sample.h)
   uint32_t def_idle, atk_idle;
 };
+// the kernarg offsets the kernels were built with: the view in front, the outputs behind it
+static_assert(offsetof(BoardView, xcd_map) == 12 && offsetof(BoardView, hdr) == 16 && offsetof(BoardView, tw_inf) == 24 &&
+                  offsetof(BoardView, cells) == 32 && offsetof(BoardView, cfg) == 40 && sizeof(BoardView) == 48,
+              "BoardView's layout");
+static_assert(offsetof(MaskArgs, v) == 0 && offsetof(MaskArgs, def_mask) == 48 && offsetof(MaskArgs, def_pitch) == 72 &&
+                  sizeof(MaskArgs) == 80, "MaskArgs' layout");
+static_assert(offsetof(SampleArgs, v) == 0 && offsetof(SampleArgs, def_act) == 48 && offsetof(SampleArgs, key) == 80 &&
+                  offsetof(SampleArgs, atk_idle) == 92 && sizeof(SampleArgs) == 96, "SampleArgs' layout");
 constexpr int kSampleWaves = 4;  // entries (waves) per workgroup, as kMaskListWaves
 // ids == nullptr: every board (cap = B, entry i is board i); else td_mask_list_kernel's contract:
 // boards ids[0 .. cap) where verdict == nullptr, else ids[0 .. *count) unless the check kernel

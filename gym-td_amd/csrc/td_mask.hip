@@ -10,17 +10,14 @@ template <int LT>
 __global__ __launch_bounds__(64) void td_mask_kernel(MaskArgs a) {
   __shared__ __attribute__((aligned(16))) uint8_t R[MaskRow<LT>::BYTES];
   const int i = blockIdx.x, lane = (int)threadIdx.x;
-  if (i >= a.B) return;
-  mask_board<LT>(a, a.xcd_map ? xcd_board(i, a.B) : i, lane, R);
+  if (i >= a.v.B) return;
+  mask_board<LT>(a, a.v.xcd_map ? xcd_board(i, a.v.B) : i, lane, R);
 }
 
 hipError_t launch_mask(const MaskArgs& a, hipStream_t s) {
-  switch (a.L) {
-    case 10: hipLaunchKernelGGL(td_mask_kernel<10>, dim3(a.B), dim3(64), 0, s, a); break;
-    case 20: hipLaunchKernelGGL(td_mask_kernel<20>, dim3(a.B), dim3(64), 0, s, a); break;
-    case 30: hipLaunchKernelGGL(td_mask_kernel<30>, dim3(a.B), dim3(64), 0, s, a); break;
-    default: hipLaunchKernelGGL(td_mask_kernel<0>, dim3(a.B), dim3(64), 0, s, a); break;
-  }
+  with_side(a.v.L, [&](auto lt) {
+    hipLaunchKernelGGL(td_mask_kernel<decltype(lt)::value>, dim3(a.v.B), dim3(64), 0, s, a);
+  });
   return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // td_mask_body.h -- the mask of one board, by one wave: the common body of td_mask_kernel
-// (td_mask.hip, every board) and td_mask_list_kernel (td_mask_list.hip, the boards of a list).
+// (td_mask.hip, every board) and td_mask_list_kernel (td_mask_list.hip, the boards of a list),
+// and in front of it the row build, which the sampler (td_sample.hip) runs too.
 // Device text only; each kernel supplies the wave's LDS row.
 //
 // The wave reads the board's header (96 B), its cell words (map[6], the build-blocking count,
@@ -24,7 +25,9 @@
 #include <cstddef>
 
 #include "td_kernels.h"
+#include "td_list_dev.h"
 #include "td_mask.h"
+#include "td_step_launch.h"
 #include "td_wave.h"
 
 namespace td {
@@ -43,24 +46,80 @@ struct MaskRow {
 template <int RB>
 __device__ __forceinline__ uint32_t row_byte(const uint8_t* R, int j) { return j < RB ? R[j] : kMaskPad; }
 
+// ---- the row build: the legality rules' one device restatement, shared with the sampler
+// (td_sample.hip).  What differs between the two stays in their bodies: the padding fill, the
+// mask's alignment shift and no-op byte, where the wave syncs, the sampler's early exit.
+
+// The board's header: 24 words, one per lane, and the values as lane broadcasts of them (TdHdr,
+// td_common.h), each evaluated where it is asked for.
+struct HdrWords {
+  static_assert(offsetof(TdHdr, cost_def) == 0 && offsetof(TdHdr, cost_atk) == 8 && offsetof(TdHdr, steps) == 24 &&
+                offsetof(TdHdr, atk_cd) == 32 && offsetof(TdHdr, def_cd) == 36 && offsetof(TdHdr, n_en) == 40 &&
+                offsetof(TdHdr, n_tw) == 44 && offsetof(TdHdr, num_roads) == 48, "TdHdr words read below");
+  uint32_t w;
+  __device__ __forceinline__ HdrWords(const TdHdr* hdr, int lane)
+      : w(lane < (int)(sizeof(TdHdr) / 4) ? reinterpret_cast<const uint32_t*>(hdr)[lane] : 0u) {}
+  __device__ __forceinline__ int word(int i) const { return (int)rdl(w, i); }
+  __device__ __forceinline__ double cost_def() const { return __hiloint2double(word(1), word(0)); }
+  __device__ __forceinline__ double cost_atk() const { return __hiloint2double(word(3), word(2)); }
+  __device__ __forceinline__ int steps() const { return word(6); }
+  __device__ __forceinline__ int atk_cd() const { return word(8); }
+  __device__ __forceinline__ int def_cd() const { return word(9); }
+  __device__ __forceinline__ int n_en() const { return word(10); }
+  __device__ __forceinline__ int n_tw() const { return word(11); }
+  __device__ __forceinline__ int num_roads() const { return word(12); }
+};
+
+// Build (ops 0-3) per cell of board b into ROW[op * NC + cell]; level-up / destruct (ops 4-5):
+// no tower there.  Then, behind the caller's wsync(), the board's n_tw <= TCAP tower lanes
+// overwrite the two entries of their own cells.  Macros, not functions, as td_copy_body.h's
+// body and for its reason: a function boundary around the cell pass changes how the compiler
+// forms the branch on NC & 3 in the generic-side kernels (two instructions, measured with
+// scripts/kernel_isa_digest.py); as macros every kernel's token stream is what it was.  In
+// scope at the expansion: v (the BoardView), C (*v.cfg), b, NC, lane, cost_def, n_tw.
+#define TD_ROW_CELLS(ROW)                                                                                        \
+  double price[4];                                                                                               \
+  _Pragma("unroll") for (int t = 0; t < 4; ++t) price[t] = C.t_price[t][0];                                      \
+  const uint32_t* const cw = v.cells + (size_t)b * NC;                                                           \
+  auto put_cell = [&](int c, uint32_t word) {                                                                    \
+    _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                                \
+        (ROW)[t * NC + c] = (uint8_t)mask_build_code(cost_def, price[t], word, n_tw);                            \
+    (ROW)[4 * NC + c] = (uint8_t)mask_lvup_code(false, 0u, cost_def, C);                                         \
+    (ROW)[5 * NC + c] = (uint8_t)mask_destruct_code(false);                                                      \
+  };                                                                                                             \
+  if ((NC & 3) == 0) { /* 16-B loads of four cells (the board's words start 16-B aligned) */                     \
+    const u32x4* const cw4 = reinterpret_cast<const u32x4*>(cw);                                                 \
+    for (int i = lane; i < NC / 4; i += 64) {                                                                    \
+      const u32x4 x = cw4[i];                                                                                    \
+      put_cell(4 * i + 0, x.x); put_cell(4 * i + 1, x.y); put_cell(4 * i + 2, x.z); put_cell(4 * i + 3, x.w);    \
+    }                                                                                                            \
+  } else {                                                                                                       \
+    for (int c = lane; c < NC; c += 64) put_cell(c, cw[c]);                                                      \
+  }
+#define TD_ROW_TOWERS(ROW)                                                                                       \
+  if (lane < n_tw) { /* (one tower per cell: no two lanes write the same byte) */                                \
+    const uint32_t ti = v.tw_inf[(size_t)b * TCAP + lane];                                                       \
+    const int c = tw_cell(ti);                                                                                   \
+    if (c < NC) {                                                                                                \
+      (ROW)[4 * NC + c] = (uint8_t)mask_lvup_code(true, ti, cost_def, C);                                        \
+      (ROW)[5 * NC + c] = (uint8_t)mask_destruct_code(true);                                                     \
+    }                                                                                                            \
+  }
+
 // R: the wave's own MaskRow<LT>::BYTES of LDS, 16-B aligned; only wsync() orders its accesses.
 template <int LT>
 __device__ __forceinline__ void mask_board(const MaskArgs& a, int b, int lane, uint8_t* const R) {
   constexpr int RB = MaskRow<LT>::BYTES;
-  const int L = LT ? LT : a.L, NC = L * L;
-  const TdDevCfg& C = *a.cfg;
+  const BoardView& v = a.v;
+  const int L = LT ? LT : v.L, NC = L * L;
+  const TdDevCfg& C = *v.cfg;
 
-  // the header: 24 words, one per lane, then lane broadcasts (TdHdr, td_common.h)
-  const uint32_t* const hw = reinterpret_cast<const uint32_t*>(a.hdr + b);
-  const uint32_t w = lane < (int)(sizeof(TdHdr) / 4) ? hw[lane] : 0u;
-  static_assert(offsetof(TdHdr, cost_def) == 0 && offsetof(TdHdr, cost_atk) == 8 && offsetof(TdHdr, steps) == 24 &&
-                offsetof(TdHdr, atk_cd) == 32 && offsetof(TdHdr, def_cd) == 36 && offsetof(TdHdr, n_en) == 40 &&
-                offsetof(TdHdr, n_tw) == 44 && offsetof(TdHdr, num_roads) == 48, "TdHdr words read below");
-  const double cost_def = __hiloint2double((int)rdl(w, 1), (int)rdl(w, 0));
-  const double cost_atk = __hiloint2double((int)rdl(w, 3), (int)rdl(w, 2));
-  const int steps = (int)rdl(w, 6), atk_cd = (int)rdl(w, 8), def_cd = (int)rdl(w, 9);
-  const int n_en = (int)rdl(w, 10), num_roads = (int)rdl(w, 12);
-  int n_tw = (int)rdl(w, 11);
+  const HdrWords hd(v.hdr + b, lane);
+  const double cost_def = hd.cost_def();
+  const double cost_atk = hd.cost_atk();
+  const int steps = hd.steps(), atk_cd = hd.atk_cd(), def_cd = hd.def_cd();
+  const int n_en = hd.n_en(), num_roads = hd.num_roads();
+  int n_tw = hd.n_tw();
   const bool live = mask_board_live(num_roads);
 
   if (a.atk_mask && lane < 15) {  // [3][5]: road, type (4 = none: always legal)
@@ -85,38 +144,12 @@ __device__ __forceinline__ void mask_board(const MaskArgs& a, int b, int lane, u
     for (int i = lane; i < RB / 16; i += 64) R4[i] = pad;
   }
   wsync();
-  // build (ops 0-3) per cell; level-up / destruct (ops 4-5): no tower there
   if (n_tw > TCAP) n_tw = TCAP;  // (never by the step's own stores: an imported header)
-  double price[4];
-#pragma unroll
-  for (int t = 0; t < 4; ++t) price[t] = C.t_price[t][0];
   uint8_t* const row = R + sh;
-  const uint32_t* const cw = a.cells + (size_t)b * NC;
-  auto put_cell = [&](int c, uint32_t word) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) row[t * NC + c] = (uint8_t)mask_build_code(cost_def, price[t], word, n_tw);
-    row[4 * NC + c] = (uint8_t)mask_lvup_code(false, 0u, cost_def, C);
-    row[5 * NC + c] = (uint8_t)mask_destruct_code(false);
-  };
-  if ((NC & 3) == 0) {  // 16-B loads of four cells (the board's words start 16-B aligned)
-    const u32x4* const cw4 = reinterpret_cast<const u32x4*>(cw);
-    for (int i = lane; i < NC / 4; i += 64) {
-      const u32x4 v = cw4[i];
-      put_cell(4 * i + 0, v.x); put_cell(4 * i + 1, v.y); put_cell(4 * i + 2, v.z); put_cell(4 * i + 3, v.w);
-    }
-  } else {
-    for (int c = lane; c < NC; c += 64) put_cell(c, cw[c]);
-  }
-  if (lane == 0 && !a.multi) row[6 * NC] = (uint8_t)kMaskAlways;  // the no-op
+  TD_ROW_CELLS(row)
+  if (lane == 0 && !v.multi) row[6 * NC] = (uint8_t)kMaskAlways;  // the no-op
   wsync();
-  if (lane < n_tw) {  // (one tower per cell: no two lanes write the same byte)
-    const uint32_t ti = a.tw_inf[(size_t)b * TCAP + lane];
-    const int c = tw_cell(ti);
-    if (c < NC) {
-      row[4 * NC + c] = (uint8_t)mask_lvup_code(true, ti, cost_def, C);
-      row[5 * NC + c] = (uint8_t)mask_destruct_code(true);
-    }
-  }
+  TD_ROW_TOWERS(row)
   wsync();
 
   // out: bytes [sh, sh + pitch) of the 16-B grid that starts at global address p0 + g - sh

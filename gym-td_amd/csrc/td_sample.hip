@@ -4,12 +4,11 @@
 //
 // Shape: td_mask_list_kernel's -- one wave per entry, kSampleWaves entries per workgroup under
 // the XCD-contiguous group map, each wave with an LDS row of its own that only wsync() orders,
-// count and verdict as wave-uniform loads through the constant address space.  ids == nullptr
-// serves every board: entry i is board i.
+// the list's length and the wave's entry as td_list_dev.h makes them.  ids == nullptr serves
+// every board: entry i is board i.
 //
-// Per board the wave puts the row of fail codes together in LDS as mask_board does
-// (td_mask_body.h: header words, cell words, tower lanes; that text is repeated here, so the
-// mask kernels compile to the code they were) and does not store it.  Lane l owns the P
+// Per board the wave puts the row of fail codes together in LDS with mask_board's row build
+// (td_mask_body.h: header words, cell pass, tower lanes) and does not store it.  Lane l owns the P
 // consecutive 16-B pieces [l P, (l + 1) P) of the row, P = ceil(pieces / 64): it counts their
 // legal bytes (mask_legal4 and one population count per piece), a wave prefix sum over the 64
 // counts gives n_def and the one lane whose range holds the k-th candidate, and
@@ -21,12 +20,8 @@
 // rounded up to 16 B (L = 32 for the generic build): 2,432 / 9,600 / 21,632 / 24,576 B at
 // L = 10 / 20 / 30 / generic.  The prefix sum runs on lane shuffles and takes no LDS
 // (a DPP row scan in its place measured the same: profiles/sample_actions/sample_bench_dpp_scan.jsonl).
-#include <cstddef>
-
-#include "td_kernels.h"
-#include "td_mask.h"
+#include "td_mask_body.h"
 #include "td_sample.h"
-#include "td_wave.h"
 
 namespace td {
 
@@ -49,20 +44,16 @@ __device__ __forceinline__ uint32_t legal16(const u32x4 x) {
 // R: the wave's own SampleRow<LT>::BYTES of LDS, 16-B aligned; only wsync() orders its accesses.
 template <int LT>
 __device__ __forceinline__ void sample_board(const SampleArgs& a, int b, int lane, uint8_t* const R) {
-  const int L = LT ? LT : a.L, NC = L * L;
-  const TdDevCfg& C = *a.cfg;
+  const BoardView& v = a.v;
+  const int L = LT ? LT : v.L, NC = L * L;
+  const TdDevCfg& C = *v.cfg;
 
-  // the header: 24 words, one per lane, then lane broadcasts (as mask_board)
-  const uint32_t* const hw = reinterpret_cast<const uint32_t*>(a.hdr + b);
-  const uint32_t w = lane < (int)(sizeof(TdHdr) / 4) ? hw[lane] : 0u;
-  static_assert(offsetof(TdHdr, cost_def) == 0 && offsetof(TdHdr, cost_atk) == 8 && offsetof(TdHdr, steps) == 24 &&
-                offsetof(TdHdr, atk_cd) == 32 && offsetof(TdHdr, def_cd) == 36 && offsetof(TdHdr, n_en) == 40 &&
-                offsetof(TdHdr, n_tw) == 44 && offsetof(TdHdr, num_roads) == 48, "TdHdr words read below");
-  const double cost_def = __hiloint2double((int)rdl(w, 1), (int)rdl(w, 0));
-  const double cost_atk = __hiloint2double((int)rdl(w, 3), (int)rdl(w, 2));
-  const int steps = (int)rdl(w, 6), atk_cd = (int)rdl(w, 8), def_cd = (int)rdl(w, 9);
-  const int n_en = (int)rdl(w, 10), num_roads = (int)rdl(w, 12);
-  int n_tw = (int)rdl(w, 11);
+  const HdrWords hd(v.hdr + b, lane);
+  const double cost_def = hd.cost_def();
+  const double cost_atk = hd.cost_atk();
+  const int steps = hd.steps(), atk_cd = hd.atk_cd(), def_cd = hd.def_cd();
+  const int n_en = hd.n_en(), num_roads = hd.num_roads();
+  int n_tw = hd.n_tw();
   const bool live = mask_board_live(num_roads);
   const uint64_t ub = (uint64_t)(uint32_t)b;
 
@@ -92,36 +83,10 @@ __device__ __forceinline__ void sample_board(const SampleArgs& a, int b, int lan
       R4[NP - 1] = pad;
     }
     wsync();
-    // build (ops 0-3) per cell; level-up / destruct (ops 4-5): no tower there
     if (n_tw > TCAP) n_tw = TCAP;  // (never by the step's own stores: an imported header)
-    double price[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) price[t] = C.t_price[t][0];
-    const uint32_t* const cw = a.cells + (size_t)b * NC;
-    auto put_cell = [&](int c, uint32_t word) {
-#pragma unroll
-      for (int t = 0; t < 4; ++t) R[t * NC + c] = (uint8_t)mask_build_code(cost_def, price[t], word, n_tw);
-      R[4 * NC + c] = (uint8_t)mask_lvup_code(false, 0u, cost_def, C);
-      R[5 * NC + c] = (uint8_t)mask_destruct_code(false);
-    };
-    if ((NC & 3) == 0) {  // 16-B loads of four cells (the board's words start 16-B aligned)
-      const u32x4* const cw4 = reinterpret_cast<const u32x4*>(cw);
-      for (int i = lane; i < NC / 4; i += 64) {
-        const u32x4 v = cw4[i];
-        put_cell(4 * i + 0, v.x); put_cell(4 * i + 1, v.y); put_cell(4 * i + 2, v.z); put_cell(4 * i + 3, v.w);
-      }
-    } else {
-      for (int c = lane; c < NC; c += 64) put_cell(c, cw[c]);
-    }
+    TD_ROW_CELLS(R)
     wsync();
-    if (lane < n_tw) {  // (one tower per cell: no two lanes write the same byte)
-      const uint32_t ti = a.tw_inf[(size_t)b * TCAP + lane];
-      const int c = tw_cell(ti);
-      if (c < NC) {
-        R[4 * NC + c] = (uint8_t)mask_lvup_code(true, ti, cost_def, C);
-        R[5 * NC + c] = (uint8_t)mask_destruct_code(true);
-      }
-    }
+    TD_ROW_TOWERS(R)
     wsync();
 
     // count: this lane's pieces [p0, p0 + P)
@@ -170,7 +135,7 @@ __device__ __forceinline__ void sample_board(const SampleArgs& a, int b, int lan
 
   if (a.def_count && lane == 0) a.def_count[b] = n_def;
   if (!a.def_act) return;
-  if (!a.multi) {
+  if (!v.multi) {
     if (lane == 0) a.def_act[b] = act >= 0 ? (int64_t)act : (int64_t)(6 * NC);  // 6 L^2: the no-op
     return;
   }
@@ -200,32 +165,20 @@ __global__ __launch_bounds__(64 * kSampleWaves) void td_sample_kernel(SampleArgs
   constexpr int RB = SampleRow<LT>::BYTES;
   __shared__ __attribute__((aligned(16))) uint8_t R[kSampleWaves][RB];
   static_assert(RB % 16 == 0, "every wave's row is 16-B aligned");
-  typedef __attribute__((address_space(4))) const int32_t cword_t;
-  int n = cap;
-  if (verdict) {
-    const int code = reinterpret_cast<cword_t*>(reinterpret_cast<uintptr_t>(verdict))[0];
-    static_assert(offsetof(td_list_status, code) == 0, "the verdict's first word");
-    if (count) n = reinterpret_cast<cword_t*>(reinterpret_cast<uintptr_t>(count))[0];
-    n = code ? 0 : n;
-  }
+  const int n = list_length(cap, count, verdict);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = (int)(threadIdx.x & 63);
-  const int groups = (n + kSampleWaves - 1) / kSampleWaves, g = (int)blockIdx.x;
-  if (g >= groups) return;
-  const int i = (a.xcd_map ? xcd_board(g, groups) : g) * kSampleWaves + wave;
-  if (i >= n) return;
-  const int b = ids ? reinterpret_cast<cword_t*>(reinterpret_cast<uintptr_t>(ids))[i] : i;
+  int i;
+  if (!list_wave_entry<kSampleWaves>(a.v.xcd_map, n, wave, &i)) return;
+  const int b = ids ? list_word(ids, i) : i;
   sample_board<LT>(a, b, lane, R[wave]);
 }
 
 hipError_t launch_sample(const SampleArgs& a, const int32_t* ids, int cap, const int32_t* count,
                          const td_list_status* verdict, hipStream_t s) {
   const dim3 grid((cap + kSampleWaves - 1) / kSampleWaves), block(64 * kSampleWaves);
-  switch (a.L) {
-    case 10: hipLaunchKernelGGL(td_sample_kernel<10>, grid, block, 0, s, a, ids, cap, count, verdict); break;
-    case 20: hipLaunchKernelGGL(td_sample_kernel<20>, grid, block, 0, s, a, ids, cap, count, verdict); break;
-    case 30: hipLaunchKernelGGL(td_sample_kernel<30>, grid, block, 0, s, a, ids, cap, count, verdict); break;
-    default: hipLaunchKernelGGL(td_sample_kernel<0>, grid, block, 0, s, a, ids, cap, count, verdict); break;
-  }
+  with_side(a.v.L, [&](auto lt) {
+    hipLaunchKernelGGL(td_sample_kernel<decltype(lt)::value>, grid, block, 0, s, a, ids, cap, count, verdict);
+  });
   return hipGetLastError();
 }
 

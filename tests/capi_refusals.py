@@ -6,7 +6,8 @@ td_last_error() text, byte for byte.
     python tests/capi_refusals.py --record PATH     # writes what the loaded library answers
 
 The golden file was recorded from the library before td_capi.hip's checks were written once each
-(select a library with TDSTEP_LIB).  Messages that carry a source line (HIP failures) are no
+(select a library with TDSTEP_LIB), the sampler's rows at its end from the library before the
+list forms of the masks and the sampler were written once.  Messages that carry a source line (HIP failures) are no
 refusals and have no row.
 
 Handles, B = 4 each, the smallest that reach every branch:
@@ -85,6 +86,39 @@ def _mask_rows(fn, tail, dev):
             (fn + " cap < 0, no output", fn, "def", dict(tail, io="none", cap=-1)),
         ]
     return rows
+
+
+def _sample_rows(fn, tail, dev):
+    """The io rows of the sampling entry points, as _mask_rows; an io kind names the outputs it has
+    (SAMPLE_OUTS)."""
+    rows = [
+        (fn + " NULL io", fn, None, dict(tail, io="null")),
+        (fn + " ABI-2 io", fn, None, dict(tail, io="abi2")),
+        (fn + " short io", fn, None, dict(tail, io="size56")),
+        (fn + " NULL handle", fn, None, dict(tail, io="ok")),
+        (fn + " no action output", fn, "def", dict(tail, io="none")),
+        (fn + " no action output, TD-atk", fn, "atk", dict(tail, io="none")),
+        (fn + " no action output, both counts", fn, "2p", dict(tail, io="counts")),
+        (fn + " def_act on TD-atk", fn, "atk", dict(tail, io="def_act")),
+        (fn + " def_count on TD-atk", fn, "atk", dict(tail, io="atk_act+def_count")),
+        (fn + " atk_act on TD-def", fn, "def", dict(tail, io="atk_act")),
+        (fn + " atk_count on TD-def", fn, "def", dict(tail, io="def_act+atk_count")),
+        (fn + " both sides on TD-def", fn, "def", dict(tail, io="both")),
+        (fn + " both sides on TD-atk", fn, "atk", dict(tail, io="both")),
+    ]
+    if dev:
+        rows += [
+            (fn + " NULL io, cap < 0", fn, None, dict(tail, io="null", cap=-1)),
+            (fn + " ABI-2 io, cap < 0", fn, None, dict(tail, io="abi2", cap=-1)),
+            (fn + " short io, cap < 0, a handle", fn, "def", dict(tail, io="size56", cap=-3)),
+            (fn + " cap < 0, NULL handle", fn, None, dict(tail, io="ok", cap=-1)),
+            (fn + " cap < 0, no action output", fn, "def", dict(tail, io="none", cap=-1)),
+        ]
+    return rows
+
+
+SAMPLE_OUTS = {"ok": ("def_act",), "abi2": ("def_act",), "size56": ("def_act",), "none": (),
+               "counts": ("def_count", "atk_count"), "both": ("def_act", "atk_act")}
 
 
 def _ids_rows(fn, io):
@@ -246,6 +280,26 @@ def table():
         (fn + " format -1", fn, "atk", dict(fmt=-1)),
         (fn + " float32 again", fn, "def", dict(fmt=0)),
     ]
+    # ---- the sampler (behind the settings: its rows were recorded later, at the golden file's end)
+    t += _sample_rows("td_sample_actions", {}, False)
+    fn = "td_sample_actions_boards"
+    t += _sample_rows(fn, dict(boards=[0], n=1), False)
+    t += _ids_rows(fn, "def_act")
+    t += [
+        (fn + " no action output, n = -1", fn, "def", dict(io="none", boards=[0], n=-1)),
+        (fn + " atk_act on TD-def, twice", fn, "def", dict(io="atk_act", boards=[1, 1], n=2)),
+        (fn + " frame skip, twice", fn, "skip", dict(io="def_act", boards=[1, 1], n=2)),
+        (fn + " random_agent = 0, n = 0", fn, "np", dict(io="def_act+def_count", boards=None, n=0)),
+    ]
+    fn = "td_sample_actions_boards_dev"
+    t += _sample_rows(fn, dict(boards="ok", cap=1), True)
+    t += _cap_rows(fn, "def_act", ["boards"])
+    t += [
+        (fn + " no action output, cap > B", fn, "def", dict(io="none", boards="ok", cap=B + 1)),
+        (fn + " def_act on TD-atk, NULL list", fn, "atk", dict(io="def_act", boards=None, cap=1)),
+        (fn + " atk_act on TD-atk, cap > B", fn, "atk", dict(io="atk_act", boards="ok", cap=B + 1)),
+        (fn + " frame skip, cap = 0", fn, "skip", dict(io="def_act", boards=None, cap=0)),
+    ]
     ids = [r[0] for r in t]
     assert len(set(ids)) == len(ids), [i for i in ids if ids.count(i) > 1]
     return t
@@ -286,6 +340,9 @@ class Fixtures:
             "def_mask": torch.zeros(B * 1024, dtype=torch.uint8, **d),
             "def_code": torch.zeros(B * 1024, dtype=torch.uint8, **d),
             "atk_mask": torch.zeros(B * 64, dtype=torch.uint8, **d),
+            "sample_atk_act": torch.zeros(B * 3 * 8, dtype=torch.int64, **d),
+            "def_count": torch.zeros(B, dtype=torch.int32, **d),
+            "atk_count": torch.zeros(B, dtype=torch.int32, **d),
             "ok": torch.arange(B, dtype=torch.int32, **d),
             "ok2": torch.arange(B, dtype=torch.int32, **d),
             "bad": torch.tensor([0, 1, B, 2], dtype=torch.int32, **d),
@@ -330,6 +387,17 @@ class Fixtures:
             io.size = 24
         return io
 
+    def sample_io(self, kind):
+        if kind == "null":
+            return None
+        outs = SAMPLE_OUTS.get(kind, tuple(kind.split("+")))
+        io = self._lib.TdSampleIO(**{k: self.ptr("sample_atk_act" if k == "atk_act" else k) for k in outs})
+        if kind == "abi2":
+            io.abi = 2
+        elif kind == "size56":
+            io.size = 56
+        return io
+
     def ids(self, v):
         """A host id array (kept alive to the end of the run), or NULL."""
         if v is None:
@@ -362,6 +430,12 @@ class Fixtures:
             rc = f(h, self.mask_io(a["io"], a.get("pitch", 0)), self.ids(a["boards"]), a["n"], None)
         elif fn == "td_action_mask_boards_dev":
             rc = f(h, self.mask_io(a["io"], a.get("pitch", 0)), self.ptr(a["boards"]), a["cap"], count, status, None)
+        elif fn == "td_sample_actions":
+            rc = f(h, self.sample_io(a["io"]), None)
+        elif fn == "td_sample_actions_boards":
+            rc = f(h, self.sample_io(a["io"]), self.ids(a["boards"]), a["n"], None)
+        elif fn == "td_sample_actions_boards_dev":
+            rc = f(h, self.sample_io(a["io"]), self.ptr(a["boards"]), a["cap"], count, status, None)
         elif fn in ("td_set_step_kernel", "td_set_retained_step_kernel"):
             rc = f(h, a["kind"])
         elif fn == "td_set_frame_skip":

@@ -24,7 +24,8 @@ def test_every_entry_point_and_every_handle_has_rows():
     assert {r[1] for r in t} == {
         "td_step", "td_step_boards", "td_step_boards_dev", "td_copy_boards", "td_copy_boards_dev", "td_action_mask",
         "td_action_mask_boards", "td_action_mask_boards_dev", "td_set_step_kernel", "td_set_retained_step_kernel",
-        "td_set_frame_skip", "td_set_obs_format"}
+        "td_set_frame_skip", "td_set_obs_format", "td_sample_actions", "td_sample_actions_boards",
+        "td_sample_actions_boards_dev"}
     assert {r[2] for r in t} == set(R.HANDLES) | {None}
     # no message with a source line (a HIP failure is no refusal); an accepted row has no message
     for rid, (rc, msg) in R.golden().items():
