@@ -34,6 +34,7 @@
 #include "td_sample.h"
 #include "td_state_rec.h"
 #include "td_step_launch.h"
+#include "td_upgrade_step.h"
 
 using namespace td;
 
@@ -200,6 +201,7 @@ void build_dev_cfg(const td_config& c, TdDevCfg& d) {
   d.max_episode_steps = c.max_episode_steps;
   d.max_cluster_length = c.max_cluster_length;
   d.max_tower_lv = c.max_tower_lv;
+  d.upgrade_step = upgrade_step(d.max_episode_steps, d.enemy_upgrade_at);
 }
 
 // The checks themselves: td_cfg_check.h (run alone by scripts/cfg_check_host.cpp).

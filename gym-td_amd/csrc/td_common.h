@@ -69,6 +69,9 @@ struct alignas(16) TdDevCfg {
   double def_init_cost, atk_init_cost;
   int32_t frozen_time, base_LP, tower_distance, atk_interval;
   int32_t def_interval, max_episode_steps, max_cluster_length, max_tower_lv;
+  // the first step count at which a summon is level 1: steps / max_episode_steps >= enemy_upgrade_at
+  // as an integer test (td_upgrade_step.h); derived from the two where the block is built
+  int32_t upgrade_step, pad_[3];
 };
 
 __host__ __device__ inline int cw_dist(uint32_t w) { return (int)((w >> 16) & 0xffu); }

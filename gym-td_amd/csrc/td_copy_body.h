@@ -156,7 +156,7 @@ __device__ __forceinline__ void copy_obs(const Smem<NC>& S, const U& u, const Ct
   Prefetch P;                                                                                                            \
   prefetch_issue<PF_SMALL, PF_SMALL>(P, a, sb, lane, ncr, false);                                                        \
   U u;                                                                                                                   \
-  load_board<NC, PF_SMALL, PF_SMALL>(S, u, x, a, sb, P);                                                                 \
+  load_board<NC, PF_SMALL, PF_SMALL, true>(S, u, x, a, sb, P);                                                           \
   enemy_stats(S, u, x);                                                                                                  \
   channel_scalars(S, u, x);                                                                                              \
   pack_obs_cells(S, x);                                                                                                  \

@@ -260,8 +260,46 @@ __device__ __forceinline__ void defender_scan(Smem<NC>& S, U& u, const Ctx& x, c
 template <int NC>
 __device__ __forceinline__ int summon_cluster(Smem<NC>& S, U& u, const Ctx& x, uint32_t types, int road, uint32_t* real) {
   const TdDevCfg& C = x.C;
-  const int lv = u.progress >= C.enemy_upgrade_at ? 1 : 0;  // :201
+  // progress >= enemy_upgrade_at (:201) as an integer test: u.progress is steps / max_episode_steps
+  // wherever a cluster is summoned (after load_board, reset_board and each board_step), and that
+  // quotient passes the threshold from upgrade_step on (td_upgrade_step.h)
+  // (a threshold no step count reaches gives INT32_MAX: the two tests then differ at steps ==
+  // INT32_MAX alone, the last value the int32 counter can hold)
+  const int lv = u.steps >= C.upgrade_step ? 1 : 0;
   const int st = u.start(road);
+  if (x.short_cuts && (types & 0xfu) <= 4u && types == (types & 0xfu) * 0x11111111u) {
+    // Eight equal types (the lv1 opponent always; an empty or a one-type cluster of a caller):
+    // the first slot that fails -- the cost, or a full list with its flag -- leaves cost_atk and
+    // the list as they were, so every later slot fails the same way.  Cost and max LP are read
+    // once, and the summoned enemies are written one per lane.
+    const int t = (int)(types & 0xfu);
+    if (t == 4) {  // nothing tried (:207-209)
+      if (real) *real = types;
+      return FC_OK;
+    }
+    const double cost = C.e_cost[t][lv], lp = C.e_lp[t][lv];
+    const int n0 = u.n;
+    int m = 0;
+    while (m < 8 && !(u.cost_atk < cost)) {                 // :212-213
+      if (n0 + m >= ECAP) { u.flags |= FLAG_EN_OVERFLOW; break; }
+      u.cost_atk = dsub(u.cost_atk, cost);                  // :215
+      m += 1;
+    }
+    if (x.lane < m) {
+      S.eLP[n0 + x.lane] = lp;
+      S.eMg[n0 + x.lane] = 0.0;
+      S.eInf[n0 + x.lane] = en_pack(st, t, lv, 0, x.ep);
+    }
+    if (m) {
+      u.n = n0 + m;
+      u.en_touch = true;  // a new enemy: its group's planes change
+    }
+    if (real) {
+      const uint32_t keep = m >= 8 ? ~0u : (1u << (4 * m)) - 1u;
+      *real = (types & keep) | (0x44444444u & ~keep);
+    }
+    return m ? FC_OK : FC_COST;                             // :219-224
+  }
   bool tried = false, summoned = false;
   uint32_t rp = 0;
   // the four types' cost (lanes 0-3) and max LP (lanes 4-7) at this level in ONE LDS read,
@@ -487,54 +525,62 @@ __device__ __forceinline__ double board_step(Smem<NC>& S, U& u, const Ctx& x, co
   }
   if (lane < u.nt) S.tCd[lane] = tcd;
 
-  // --- kills (:313-317): every enemy at LP 0 was hit this step
-  bool dead0 = val[0] && lp[0] == 0.0, dead1 = val[1] && lp[1] == 0.0;
-  const int nk = popc64(ballot(dead0)) + popc64(ballot(dead1));
-  reward = dadd(reward, dmul(C.reward_kill, (double)nk));  // :315
+  // A board without an enemy (most boards, most steps) has nobody to kill, march, leak or
+  // compact: the list stays empty.  Its reward is the one the full path gives: dadd(0.0,
+  // reward_time) is never -0.0, and the kill term adds reward_kill x 0 = +-0 to it (finite
+  // values only: td_cfg_check.h), which changes no bit.
+  if (!x.short_cuts || n != 0) {
+    // --- kills (:313-317): every enemy at LP 0 was hit this step
+    bool dead0 = val[0] && lp[0] == 0.0, dead1 = val[1] && lp[1] == 0.0;
+    const int nk = popc64(ballot(dead0)) + popc64(ballot(dead1));
+    reward = dadd(reward, dmul(C.reward_kill, (double)nk));  // :315
 
-  // --- march (:319-344)
-  bool alive[2] = {val[0] && !dead0, val[1] && !dead1};
-  bool leak[2] = {false, false};
-  bool walked = false;  // the enemy entered a new cell (or leaked)
+    // --- march (:319-344)
+    bool alive[2] = {val[0] && !dead0, val[1] && !dead1};
+    bool leak[2] = {false, false};
+    bool walked = false;  // the enemy entered a new cell (or leaked)
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    if (!alive[s]) continue;
-    const uint32_t e = inf[s];
-    const int t = en_type(e), lv = en_lv(e);
-    int slow = en_slow(e), cell = en_cell(e);
-    const double sp = captured(x, en_ep(e), [&](const TdDevCfg& c) { return c.e_speed[t][lv]; });
-    if (slow > 0) { mg[s] = dadd(mg[s], dmul(sp, C.frozen_ratio)); slow -= 1; }
-    else mg[s] = dadd(mg[s], sp);
-    while (mg[s] >= 1.0) {
-      walked = true;
-      mg[s] = dsub(mg[s], 1.0);
-      const int d = pk_dir(S.cell[cell]);
-      // map[5] codes (TDBoard.py:319): 0:+c 1:-c 2:+r 3:-r
-      const int r1 = div_side(cell, x.Lm);
-      int r = r1 + (d == 2) - (d == 3), c = cell - r1 * L + (d == 0) - (d == 1);
-      if (r < 0 || r >= L || c < 0 || c >= L) { u.flags |= FLAG_BAD_MOVE; break; }
-      cell = r * L + c;
-      if (cell == u.end_cell) { leak[s] = true; break; }
+    for (int s = 0; s < 2; ++s) {
+      if (!alive[s]) continue;
+      const uint32_t e = inf[s];
+      const int t = en_type(e), lv = en_lv(e);
+      int slow = en_slow(e), cell = en_cell(e);
+      const double sp = captured(x, en_ep(e), [&](const TdDevCfg& c) { return c.e_speed[t][lv]; });
+      if (slow > 0) { mg[s] = dadd(mg[s], dmul(sp, C.frozen_ratio)); slow -= 1; }
+      else mg[s] = dadd(mg[s], sp);
+      while (mg[s] >= 1.0) {
+        walked = true;
+        mg[s] = dsub(mg[s], 1.0);
+        const int d = pk_dir(S.cell[cell]);
+        // map[5] codes (TDBoard.py:319): 0:+c 1:-c 2:+r 3:-r
+        const int r1 = div_side(cell, x.Lm);
+        int r = r1 + (d == 2) - (d == 3), c = cell - r1 * L + (d == 0) - (d == 1);
+        if (r < 0 || r >= L || c < 0 || c >= L) { u.flags |= FLAG_BAD_MOVE; break; }
+        cell = r * L + c;
+        if (cell == u.end_cell) { leak[s] = true; break; }
+      }
+      inf[s] = en_pack(cell, t, lv, slow, en_ep(e));
     }
-    inf[s] = en_pack(cell, t, lv, slow, en_ep(e));
+    // a bad move is rare and lane-local: fold the flag into the uniform copy
+    if (ballot((u.flags & FLAG_BAD_MOVE) != 0)) u.flags |= FLAG_BAD_MOVE;
+    if (ballot(walked)) u.en_touch = true;
+    const int nl = popc64(ballot(leak[0])) + popc64(ballot(leak[1]));
+    for (int p = 0; p < nl; ++p) {                            // :336-343, in list order
+      if (u.base_LP > 0) reward = dsub(reward, C.penalty_leak);
+      u.base_LP = u.base_LP - 1 > 0 ? u.base_LP - 1 : 0;
+    }
+    // --- compact survivors, list order kept (:316-317, :345-346)
+    bool keep0 = alive[0] && !leak[0], keep1 = alive[1] && !leak[1];
+    const uint64_t k0 = ballot(keep0), k1 = ballot(keep1);
+    const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const int n2 = popc64(k0) + popc64(k1);
+    wsync();
+    if (keep0) { int d = popc64(k0 & lt); S.eLP[d] = lp[0]; S.eMg[d] = mg[0]; S.eInf[d] = inf[0]; }
+    if (keep1) { int d = popc64(k0) + popc64(k1 & lt); S.eLP[d] = lp[1]; S.eMg[d] = mg[1]; S.eInf[d] = inf[1]; }
+    u.n = n2;
+  } else {
+    wsync();
   }
-  // a bad move is rare and lane-local: fold the flag into the uniform copy
-  if (ballot((u.flags & FLAG_BAD_MOVE) != 0)) u.flags |= FLAG_BAD_MOVE;
-  if (ballot(walked)) u.en_touch = true;
-  const int nl = popc64(ballot(leak[0])) + popc64(ballot(leak[1]));
-  for (int p = 0; p < nl; ++p) {                            // :336-343, in list order
-    if (u.base_LP > 0) reward = dsub(reward, C.penalty_leak);
-    u.base_LP = u.base_LP - 1 > 0 ? u.base_LP - 1 : 0;
-  }
-  // --- compact survivors, list order kept (:316-317, :345-346)
-  bool keep0 = alive[0] && !leak[0], keep1 = alive[1] && !leak[1];
-  const uint64_t k0 = ballot(keep0), k1 = ballot(keep1);
-  const uint64_t lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-  const int n2 = popc64(k0) + popc64(k1);
-  wsync();
-  if (keep0) { int d = popc64(k0 & lt); S.eLP[d] = lp[0]; S.eMg[d] = mg[0]; S.eInf[d] = inf[0]; }
-  if (keep1) { int d = popc64(k0) + popc64(k1 & lt); S.eLP[d] = lp[1]; S.eMg[d] = mg[1]; S.eInf[d] = inf[1]; }
-  u.n = n2;
 
   // --- costs (:348-353)
   double rate;

@@ -14,7 +14,7 @@ __global__ __launch_bounds__(128) TD_SMALL2_ATTR void TD_SMALL2_NAME(StepArgs a_
   const int b = a.xcd_map ? xcd_board((int)blockIdx.x, a.B) : (int)blockIdx.x;
   const int lane = (int)threadIdx.x & 63;
   if (threadIdx.x < 64) {
-    const Ctx x{S.cfg, LT, NC, lane, a.cfgs, a.epoch};
+    const Ctx x{S.cfg, LT, NC, lane, a.cfgs, a.epoch, side_magic(LT), false};
     const uint4 cfgv = load_cfg(a.cfg, lane);
     Prefetch P;
     prefetch_issue<PF_SMALL, PF_SMALL>(P, a, b, lane, NC, MODE != MODE_ATK && !a.multi);

@@ -93,6 +93,12 @@ struct Ctx {
   const TdDevCfg* tab;  // every epoch's block (HBM)
   int ep;
   uint32_t Lm = side_magic(L);  // div_side's multiplier
+  // The equal-type cluster loop of summon_cluster and board_step's empty-list skip are compiled in.
+  // A constant where the kernel builds its Ctx (everything is inlined): the two-wave kernels pass
+  // false and keep the unrolled cluster and the unconditional kills-to-compaction stretch -- their
+  // non-skipping launch at 65,536 boards, bound by its store stream, measured 0.3 % slower with the
+  // two (DESIGN section 5 "Uniform words").
+  bool short_cuts = true;
 };
 
 // A value an enemy or tower captured when it was created or upgraded (TDElements.py:
@@ -173,7 +179,10 @@ __device__ __forceinline__ double lane_f64(uint32_t v, int l) {
 }
 
 // Commit the prefetched inputs of board b into the LDS image and the scalar state.
-template <int NC, int PFE, int PFT>
+// PROGRESS: u.progress is computed here (an f64 division sequence).  Only a caller that renders
+// the loaded board as it is asks for it (the board copy: channel 13): a step's summons test the
+// step count (summon_cluster), and board_step computes the quotient every later reader uses.
+template <int NC, int PFE, int PFT, bool PROGRESS = false>
 __device__ __forceinline__ void load_board(Smem<NC>& S, U& u, const Ctx& x, const StepArgs& a, int b, const Prefetch& P) {
   const size_t eb = (size_t)b * ECAP, cb = (size_t)b * x.NCr;
   if ((x.NCr & 3) == 0) {
@@ -212,7 +221,8 @@ __device__ __forceinline__ void load_board(Smem<NC>& S, U& u, const Ctx& x, cons
   u.maxdist = (int)lane_word(P.w, 17); u.flags = (int)lane_word(P.w, 18); u.episodes = (int)lane_word(P.w, 19);
   if (x.lane == 0) S.flags0 = u.flags;
   u.max_cost = lane_f64(P.w, 20); u.max_base_LP = (int)lane_word(P.w, 22);
-  u.progress = ddiv((double)u.steps, (double)x.C.max_episode_steps);
+  if constexpr (PROGRESS) u.progress = ddiv((double)u.steps, (double)x.C.max_episode_steps);
+  else u.progress = __builtin_nan("");  // board_step sets it before any reader; a read before that shows as a NaN
   u.cells_dirty = false;
   u.tw_dirty = false;
   u.en_touch = false;
