@@ -65,4 +65,42 @@ inline bool sample_io_refused(const char* fn, const SampleIoSeen& v, unsigned wa
   return true;
 }
 
+// What td_playout and its list forms refuse of their io and of the handle's settings, in this
+// order: a NULL io, a bad size / abi word, a NULL handle, steps outside [1, max_steps], a missing
+// reward or done, a first action for a side the mode lacks, a multi-action handle, random_agent
+// = 0.  The caller fills in everything behind the header words only once they match, and the
+// handle's settings only where there is a handle.  mode: 0 TD-def, 1 TD-atk, 2 TD-2p.
+struct PlayoutIoSeen {
+  bool io = false;                // io != NULL
+  unsigned size = 0, abi = 0;     // its two header words
+  bool handle = false;            // h != NULL
+  int steps = 0;                  // io->steps
+  bool reward = false, done = false, first_def = false, first_atk = false;  // != NULL
+  int mode = 0, multi = 0, opp_np = 0;  // the handle's
+};
+inline bool playout_io_header_ok(const PlayoutIoSeen& v, unsigned want_size, int want_abi) {
+  return v.io && v.size == want_size && v.abi == (unsigned)want_abi;
+}
+inline bool playout_io_refused(const char* fn, const PlayoutIoSeen& v, unsigned want_size, int want_abi, int max_steps,
+                               char* msg, size_t n) {
+  if (!v.io) std::snprintf(msg, n, "%s: NULL io", fn);
+  else if (!playout_io_header_ok(v, want_size, want_abi))
+    std::snprintf(msg, n, "%s: td_playout_io has size %u / abi %u, this library expects size %u / abi %d "
+                  "(call td_playout_io_init)", fn, v.size, v.abi, want_size, want_abi);
+  else if (!v.handle) std::snprintf(msg, n, "%s: NULL handle", fn);
+  else if (v.steps < 1 || v.steps > max_steps)
+    std::snprintf(msg, n, "%s: steps = %d outside [1, %d] (TD_MAX_PLAYOUT_STEPS)", fn, v.steps, max_steps);
+  else if (!v.reward || !v.done) std::snprintf(msg, n, "%s: reward and done are required", fn);
+  else if (v.first_def && v.mode == 1) std::snprintf(msg, n, "%s: TD-atk has no defender side (first_def)", fn);
+  else if (v.first_atk && v.mode == 0) std::snprintf(msg, n, "%s: TD-def has no attacker side (first_atk)", fn);
+  else if (v.multi)
+    std::snprintf(msg, n, "%s: not supported with multi-action (the playout samples one discrete action per side and "
+                  "sub-step)", fn);
+  else if (v.opp_np)
+    std::snprintf(msg, n, "%s: not supported with random_agent = 0 (the built-in opponent would draw from the layout "
+                  "stream inside the launch)", fn);
+  else return false;
+  return true;
+}
+
 }  // namespace td

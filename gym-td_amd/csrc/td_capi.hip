@@ -90,7 +90,7 @@ constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw doe
 constexpr int kIdSlots = 4;      // td_copy_boards, td_step_boards: id uploads in flight before a call waits for the oldest
 // The strings the kernel-name accessors hand out: one slot each, so a name stays valid until
 // its own accessor is called again (kept_name).
-enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_SLOTS };
+enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_PLAYOUT, NAME_SLOTS };
 
 }  // namespace
 
@@ -101,7 +101,7 @@ struct td_handle {
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
-  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name
+  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name, td_playout_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -493,26 +493,35 @@ BoardView board_view(const td_handle* h) {
   return {h->B, h->L, h->multi, h->xcd_map, h->d_hdr, h->d_tw_inf, h->d_cells, h->d_cfg + h->epoch};
 }
 
-// The list forms of the calls that only read state (the masks, the sampler), each written once
-// over the call's io check and its list kernel's launch.  They are no launches for the refill
-// cadence or the ring guard, take no timing pair and leave the observation ledger alone.
-template <class Io, class Args>
-using IoCheck = int (*)(const char* fn, const td_handle* h, const Io* io, Args* out);
+// The list forms of the calls that take an io and serve a list with one kernel family (the masks,
+// the sampler, the playouts), each written once over the call's io check and its list kernel's
+// launch.  The masks and the sampler only read state: no launches for the refill cadence or the
+// ring guard, no timing pair, the observation ledger left alone; a playout's launch function
+// brackets its kernel as a partial step's (launch_playout_call).
+// H: `const td_handle` for the calls that only read state, `td_handle` for a call whose launch counts
+// in the handle (the playouts).
+template <class Io, class Args, class H = const td_handle>
+using IoCheck = int (*)(const char* fn, H* h, const Io* io, Args* out);
 template <class Args>
 using ListLaunch = hipError_t (*)(const Args& a, const int32_t* ids, int cap, const int32_t* count,
                                   const td_list_status* verdict, hipStream_t s);
+// What a call puts on the stream in front of its ids or its list check (the playouts: the refill
+// and the ring guard, where td_step_boards[_dev] put them); nullptr: nothing.
+template <class Args>
+using ListBefore = int (*)(const Args& a, hipStream_t s);
 
 // A host list.  Everything is checked here, before anything is enqueued; the ids reach the kernel
 // through the pinned id slots and d_pairs (upload_ids), as td_step_boards'.
-template <class Io, class Args>
-int read_boards(const char* fn, IoCheck<Io, Args> check, ListLaunch<Args> launch, td_handle* h, const Io* io,
-                const int32_t* boards, int n, void* stream) {
+template <class Io, class Args, class H>
+int read_boards(const char* fn, IoCheck<Io, Args, H> check, ListLaunch<Args> launch, td_handle* h, const Io* io,
+                const int32_t* boards, int n, void* stream, ListBefore<Args> before = nullptr) {
   Args a;
   if (check(fn, h, io, &a)) return -1;
   char msg[200];
   if (ids_check(boards, n, h->B, h->id_role, msg, sizeof msg) != IDS_OK) return fail("%s: %s", fn, msg);
   if (n == 0) return 0;
   hipStream_t s = (hipStream_t)stream;
+  if (before && before(a, s)) return -1;
   if (upload_ids(h, boards, nullptr, n, s)) return -1;
   HIP_OK(launch(a, h->d_pairs, n, nullptr, nullptr, s));
   return 0;
@@ -521,15 +530,16 @@ int read_boards(const char* fn, IoCheck<Io, Args> check, ListLaunch<Args> launch
 // A list, its length and its verdict in device memory, under td_step_boards_dev's contract: the
 // host checks what it can see, the check kernel the contents, on the stream in front of the list
 // kernel (the call takes the next serial); a refused list writes no output byte.
-template <class Io, class Args>
-int read_boards_dev(const char* fn, IoCheck<Io, Args> check, ListLaunch<Args> launch, td_handle* h, const Io* io,
+template <class Io, class Args, class H>
+int read_boards_dev(const char* fn, IoCheck<Io, Args, H> check, ListLaunch<Args> launch, td_handle* h, const Io* io,
                     const int32_t* boards_dev, int cap, const int32_t* count_dev, td_list_status* status_dev,
-                    void* stream) {
+                    void* stream, ListBefore<Args> before = nullptr) {
   if (negative_cap_refused(fn, io, cap)) return -1;
   Args a;
   if (check(fn, h, io, &a)) return -1;
   if (const int go = check_list_args(fn, cap, h->B, boards_dev, "boards_dev"); go <= 0) return go;
   hipStream_t s = (hipStream_t)stream;
+  if (before && before(a, s)) return -1;
   if (enqueue_list_check(h, nullptr, boards_dev, cap, count_dev, status_dev, s)) return -1;
   HIP_OK(launch(a, boards_dev, cap, count_dev, &h->d_list->verdict, s));
   return 0;
@@ -1280,6 +1290,106 @@ const char* td_sample_actions_kernel_name(td_handle* h) {
   char buf[64];
   std::snprintf(buf, sizeof buf, "td_sample_kernel<%d>", with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
   return kept_name(h, NAME_SAMPLE, buf);
+}
+
+void td_playout_io_init(td_playout_io* io) { io_init(io); }
+
+namespace {
+
+// What a playout's launch needs: the handle (the launch counts for its cadences), the step
+// arguments with the io's outputs, and the playout's own.  The list is filled in at the launch.
+struct PlayoutCall {
+  td_handle* h;
+  StepArgs a;
+  PlayoutArgs p;
+};
+
+// What td_playout and its list forms check of their io and of the handle's settings
+// (td_call_check.h playout_io_refused), and the call they make of it.  fn: the caller's name.
+int check_playout_io(const char* fn, td_handle* h, const td_playout_io* io, PlayoutCall* out) {
+  PlayoutIoSeen v;
+  v.io = io != nullptr;
+  if (io) { v.size = io->size; v.abi = io->abi; }
+  v.handle = h != nullptr;
+  if (playout_io_header_ok(v, (unsigned)sizeof(td_playout_io), TD_ABI_VERSION)) {
+    v.steps = io->steps;
+    v.reward = io->reward; v.done = io->done; v.first_def = io->first_def; v.first_atk = io->first_atk;
+    if (h) { v.mode = h->mode; v.multi = h->multi; v.opp_np = h->opp_np; }
+  }
+  char msg[240];
+  if (playout_io_refused(fn, v, (unsigned)sizeof(td_playout_io), TD_ABI_VERSION, TD_MAX_PLAYOUT_STEPS, msg, sizeof msg))
+    return fail("%s", msg);
+  out->h = h;
+  StepArgs& a = out->a;
+  a = base_args(h);
+  a.frame_skip = io->steps;  // the sub-steps of this launch; td_frame_skip() plays no part
+  a.reward = io->reward; a.done = io->done; a.win = io->win; a.allow_next = io->allow_next; a.cooldowns = io->cooldowns;
+  a.ep_return = io->ep_return; a.ep_len = io->ep_len;
+  a.ep_stats = h->d_epstats;
+  a.last_ep = h->d_lastep;
+  out->p = PlayoutArgs{};
+  out->p.key0 = sample_sm(io->seed);
+  out->p.ticket = io->ticket;
+  out->p.def_idle = io->def_idle; out->p.atk_idle = io->atk_idle;
+  out->p.steps_run = io->steps_run; out->p.first_def = io->first_def; out->p.first_atk = io->first_atk;
+  return 0;
+}
+
+// The partial step's launch bracket, in td_step_boards[_dev]'s order on the stream: the refill at
+// its cadence and the ring guard (playout_before), then the ids or the list check (read_boards,
+// read_boards_dev), then the kernel with one timing pair, one launch counted and the retained
+// observation left behind (the boards' states change and no row is written).  From the first
+// enqueue on, a step that fails leaves the retained observation behind too, as ObsLedger::Guard
+// does for the partial step.
+int playout_before(const PlayoutCall& c, hipStream_t s) {
+  if (before_step_launch(c.h, c.a, s)) {
+    c.h->ledger.touch();
+    return -1;
+  }
+  return 0;
+}
+
+// ids == nullptr: every board.
+hipError_t launch_playout_call(const PlayoutCall& c, const int32_t* ids, int cap, const int32_t* count,
+                               const td_list_status* verdict, hipStream_t s) {
+  td_handle* const h = c.h;
+  PlayoutArgs p = c.p;
+  p.ids = ids; p.cap = cap; p.count = count; p.verdict = verdict;
+  h->ledger.touch();
+  const EvPair ev = next_timing_pair(h);  // whatever `every` is (as the list calls')
+  const hipError_t e = launch_playout(c.a, p, cap, s, ev.e0, ev.e1);
+  if (e == hipSuccess) step_launched(h);
+  return e;
+}
+
+}  // namespace
+
+// One kernel on the step's stream; nothing is waited for.
+int td_playout(td_handle* h, const td_playout_io* io, void* stream) {
+  PlayoutCall c;
+  if (check_playout_io("td_playout", h, io, &c)) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  if (playout_before(c, s)) return -1;
+  HIP_OK(launch_playout_call(c, nullptr, h->B, nullptr, nullptr, s));
+  return 0;
+}
+
+// The boards named, every other board and output row left as it is.
+int td_playout_boards(td_handle* h, const td_playout_io* io, const int32_t* boards, int n, void* stream) {
+  return read_boards("td_playout_boards", check_playout_io, launch_playout_call, h, io, boards, n, stream, playout_before);
+}
+
+int td_playout_boards_dev(td_handle* h, const td_playout_io* io, const int32_t* boards_dev, int cap,
+                          const int32_t* count_dev, td_list_status* status_dev, void* stream) {
+  return read_boards_dev("td_playout_boards_dev", check_playout_io, launch_playout_call, h, io, boards_dev, cap, count_dev,
+                         status_dev, stream, playout_before);
+}
+
+const char* td_playout_kernel_name(td_handle* h) {
+  if (!h) return "";
+  StepArgs a = base_args(h);
+  a.multi = 0;  // (a multi-action handle is refused: the discrete row's name)
+  return kept_name(h, NAME_PLAYOUT, kernel_display_name(playout_row(a)));
 }
 
 // Both kernel-kind setters: the kind is checked against the map side (td_kernel_choice.h

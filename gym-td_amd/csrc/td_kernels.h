@@ -120,6 +120,28 @@ KernelRow sel_row_f16(const StepArgs& a);
 KernelRow list_row_f32(const StepArgs& a);
 KernelRow list_row_f16(const StepArgs& a);
 
+// What a playout kernel takes beside its StepArgs (td_playout, td_playout_boards[_dev];
+// td_playout.h): the sampler's call (td_sample.h: key0 = sample_sm(seed), so sub-step j's key is
+// sample_sm(key0 + ticket + j)), the entries it serves and the outputs a step does not have.
+// StepArgs::frame_skip carries the number of sub-steps; its output pointers carry the rest.
+struct PlayoutArgs {
+  uint64_t key0;
+  uint64_t ticket;
+  uint32_t def_idle, atk_idle;
+  // ids == nullptr: every board (entry i is board i).  Else td_sample_kernel's contract: boards
+  // ids[0 .. cap) where verdict == nullptr, else ids[0 .. *count) (count == nullptr: cap) unless
+  // the check kernel launched in front refused the list.
+  const int32_t* ids;
+  int cap;
+  const int32_t* count;
+  const td_list_status* verdict;
+  int32_t* steps_run;    // [B] sub-steps executed, or nullptr
+  int64_t* first_def;    // [B] the defender's action of sub-step 0, or nullptr
+  int64_t* first_atk;    // [B][3][8] the attacker's, or nullptr
+};
+// The playout unit's row (td_playout.hip): one kernel per (side, mode), no SCAN parameter.
+KernelRow playout_row(const StepArgs& a);
+
 // TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
 hipError_t launch_reset(const StepArgs& a, hipStream_t s);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),

@@ -136,6 +136,15 @@ inline hipError_t launch_step_list(const StepArgs& a, const int32_t* ids, int ca
   return launch_row(list_row(a), cap, args, s, ev0, ev1);
 }
 
+// Playouts (td_playout, td_playout_boards[_dev]): a.frame_skip sub-steps for the entries p names,
+// one block per entry of `grid` (a.B for every board, the list's n or cap).  Discrete actions,
+// random_agent=True only.
+inline hipError_t launch_playout(const StepArgs& a, const PlayoutArgs& p, int grid, hipStream_t s,
+                                 hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+  void* args[] = {const_cast<StepArgs*>(&a), const_cast<PlayoutArgs*>(&p)};
+  return launch_row(playout_row(a), grid, args, s, ev0, ev1);
+}
+
 // Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute units:
 // the batch size up to which a step runs as one round of waves of the one-wave (waves = 1,
 // td_step_kernel_small) or two-wave (td_step_kernel_small2) kernel of the format a.obs_f16.

@@ -21,6 +21,7 @@ ABI_VERSION = 3  # include/tdstep.h TD_ABI_VERSION
 STEP_KERNELS = {"auto": 0, "large": 1, "small": 2, "small2": 3}  # enum td_step_kernel_kind
 OBS_F32, OBS_F16 = 0, 1  # enum td_obs_format
 MAX_FRAME_SKIP = 16  # TD_MAX_FRAME_SKIP
+MAX_PLAYOUT_STEPS = 4096  # TD_MAX_PLAYOUT_STEPS
 
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -88,6 +89,21 @@ class TdSampleIO(ctypes.Structure):
         super().__init__(**kw)
 
 
+class TdPlayoutIO(ctypes.Structure):
+    """struct td_playout_io (tdstep.h): the size / ABI header, the sub-steps, the sampler's idle
+    probabilities, seed and ticket, then the device outputs."""
+    _fields_ = [("size", ctypes.c_uint32), ("abi", ctypes.c_uint32), ("steps", ctypes.c_int32),
+                ("def_idle", ctypes.c_uint32), ("atk_idle", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("seed", ctypes.c_uint64), ("ticket", ctypes.c_uint64)] + [(n, c_vp) for n in (
+                    "reward", "done", "steps_run", "win", "allow_next", "cooldowns", "ep_return", "ep_len",
+                    "first_def", "first_atk")]
+
+    def __init__(self, **kw):
+        kw.setdefault("size", ctypes.sizeof(TdPlayoutIO))
+        kw.setdefault("abi", ABI_VERSION)
+        super().__init__(**kw)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("libtdstep.so not found at %s -- build it with `make -C gym-td_amd/csrc` "
@@ -134,6 +150,11 @@ def _load():
         "td_sample_actions_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleIO), c_vp, ctypes.c_int, c_vp, c_vp,
                                                         c_vp]),
         "td_sample_actions_kernel_name": (ctypes.c_char_p, [c_vp]),
+        "td_playout_io_init": (None, [ctypes.POINTER(TdPlayoutIO)]),
+        "td_playout": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp]),
+        "td_playout_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp, ctypes.c_int, c_vp]),
+        "td_playout_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+        "td_playout_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
         "td_layout_from_roads": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_u32p]),
         "td_layout_generate": (ctypes.c_int, [c_u32p, ctypes.c_int, ctypes.c_int, c_u32p]),

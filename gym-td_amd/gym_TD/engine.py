@@ -747,6 +747,98 @@ class TDEngine(object):
         'td_sample_kernel<10>'."""
         return _lib.lib.td_sample_actions_kernel_name(self._h).decode()
 
+    # ---------------------------------------------------------------- playouts
+    def _playout_prepare(self, steps, ticket, def_idle, atk_idle, first):
+        """The engine's playout buffers (allocated on first use) as a td_playout_io for this
+        call's ticket, and the tickets the call takes of the engine's sampling counter:
+        ``ticket=None`` starts at the counter, which advances by ``steps`` once the call is accepted
+        (sub-step j draws at ticket + j); a refused call takes none."""
+        B = self.B
+        steps = int(steps)
+        buf = getattr(self, "_playout_buf", None)
+        if buf is None:
+            z = lambda dt: torch.zeros(B, dtype=dt, device=self.device)  # noqa: E731
+            buf = self._playout_buf = {
+                "reward": z(torch.float64), "done": z(torch.uint8), "steps_run": z(torch.int32), "win": z(torch.int8),
+                "allow_next": z(torch.uint8), "cooldowns": z(torch.uint8), "ep_return": z(torch.float64),
+                "ep_len": z(torch.int32), "first_def": None, "first_atk": None}
+        if first:
+            if self.mode != "atk" and buf["first_def"] is None:
+                buf["first_def"] = torch.full((B,), 6 * self.L * self.L, dtype=torch.int64, device=self.device)
+            if self.mode != "def" and buf["first_atk"] is None:
+                buf["first_atk"] = torch.full((B, 3, 8), 4, dtype=torch.int64, device=self.device)
+        advance = 0  # the counter moves once the library has accepted the call (_playout_done)
+        if ticket is None:
+            ticket, advance = self._sample_ticket, steps
+        io = _lib.TdPlayoutIO(steps=steps, seed=self.sample_seed, ticket=int(ticket) & sampling.M64,
+                              def_idle=sampling.idle_units(def_idle), atk_idle=sampling.idle_units(atk_idle))
+        out = dict(buf)
+        if not first:
+            out["first_def"] = out["first_atk"] = None
+        for name, t in out.items():
+            setattr(io, name, t.data_ptr() if t is not None else None)
+        return io, out, advance
+
+    def _playout_done(self, rc, advance):
+        """A playout call's return code checked; only an accepted call takes its tickets."""
+        _lib.check(rc)
+        self._sample_ticket = (self._sample_ticket + advance) & sampling.M64
+
+    def playout(self, steps, boards=None, ticket=None, def_idle=0.0, atk_idle=0.0, first=False):
+        """Random playouts on the device (td_playout, td_playout_boards): every board -- or the
+        boards named in ``boards``, under ``step_boards``' rules -- is played on for up to
+        ``steps`` board steps under the uniform random legal policy, in one kernel and with no
+        observation written.  Sub-step j is ``sample_actions_boards`` at ticket + j followed by
+        ``step_boards`` (gym_TD.sampling.reference_playout states it on the CPU); a board stops
+        after the sub-step that ends its episode, and with auto-reset starts its next one there.
+
+        Returns a dict of the engine's own device tensors, full-batch and indexed by board id
+        (allocated on first use, only the played rows overwritten by the next call):
+        ``"reward"`` float64 (the sub-steps' rewards added left to right), ``"done"`` uint8,
+        ``"steps_run"`` int32, ``"win"``, ``"allow_next"``, ``"cooldowns"``, ``"ep_return"``,
+        ``"ep_len"`` as the last executed sub-step would have written them, and with ``first``
+        ``"first_def"`` int64 (B,) / ``"first_atk"`` int64 (B, 3, 8): the actions of sub-step 0
+        (None without ``first`` and for a side the mode lacks).
+        ``ticket=None`` takes the engine's sampling counter and advances it by ``steps`` (a refused
+        call takes no ticket).
+        ``self.obs`` is not written: the next step writes every byte of it.  One kernel on
+        torch's current stream, which must be the stream of step(); nothing is synchronised.
+        TDError, nothing changed: ``steps`` outside 1 .. 4096, multi-action, random_agent=False,
+        an id out of range or named twice."""
+        io, out, advance = self._playout_prepare(steps, ticket, def_idle, atk_idle, first)
+        if boards is None:
+            self._changed()
+            self._playout_done(_lib.lib.td_playout(self._h, io, self._stream()), advance)
+        else:
+            ids = _board_ids(boards)
+            self._changed(("host", ids.copy()))
+            self._playout_done(_lib.lib.td_playout_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()),
+                               advance)
+        return out
+
+    def playout_boards_dev(self, boards, steps, count=None, status=None, ticket=None, def_idle=0.0, atk_idle=0.0,
+                           first=False):
+        """``playout`` for ids that are on the device (td_playout_boards_dev): nothing is copied to
+        the host or waited for.  ``boards``, ``count`` and ``status`` as in ``step_boards_dev``; a
+        list the device refuses changes no byte (``list_errors()``).  The tensors stay alive
+        until the next call."""
+        ids = _dev_ids(boards, self.device, "playout")
+        c = _dev_words(count, 1, self.device, "count")
+        st = _dev_words(status, 4, self.device, "status")
+        io, out, advance = self._playout_prepare(steps, ticket, def_idle, atk_idle, first)
+        self._changed(("dev", ids, c))
+        self._playout_done(_lib.lib.td_playout_boards_dev(self._h, io, ids.data_ptr(), int(ids.numel()),
+                                                          c.data_ptr() if c is not None else None,
+                                                          st.data_ptr() if st is not None else None, self._stream()),
+                           advance)
+        self._keep_playout_list = (ids, c, st)  # alive until the next call's kernels are behind them on the stream
+        return out
+
+    def playout_kernel_name(self):
+        """The kernel the three playout calls launch (td_playout_kernel_name), e.g.
+        'td_playout_kernel<10, 0>'."""
+        return _lib.lib.td_playout_kernel_name(self._h).decode()
+
     def _changed(self, rows=None):
         """Called in front of every call that can change a board or the config: the state
         serial advances.  rows: the boards the call can change, ``("host", int32 array)`` or

@@ -438,6 +438,28 @@ class TDVecEnv(object):
         search iteration -- fork, sample, step -- without a host round trip."""
         return self._sampled(self.engine.sample_actions_boards_dev(boards, count, status, ticket, def_idle, atk_idle))
 
+    def playout(self, steps, boards=None, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """Random playouts of every env, or of the envs named in ``boards``
+        (TDEngine.playout): up to ``steps`` board steps under the uniform random legal policy in
+        one kernel, no observation written.  Returns (returns, dones, lengths): the engine's
+        full-batch device tensors ``reward`` float64, ``done`` uint8 and ``steps_run`` int32,
+        the played rows fresh.  With ``action_mask=True`` the masks are computed again for the
+        states the playout left (the named rows alone where the engine knows the others are
+        current), the same bytes as ``action_masks()`` would compute."""
+        out = self.engine.playout(steps, boards, ticket, def_idle, atk_idle)
+        if self.with_action_mask:
+            self._masks = self.engine.refresh_action_mask() if boards is not None else self.engine.action_mask()
+        return out["reward"], out["done"], out["steps_run"]
+
+    def playout_dev(self, boards, steps, count=None, status=None, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """playout() for env ids that are on the device (TDEngine.playout_boards_dev): with
+        fork_dev() and step_boards_dev() a search iteration -- fork, step the chosen move, play
+        out -- without a host round trip.  ``count`` / ``status`` as in fork_dev()."""
+        out = self.engine.playout_boards_dev(boards, steps, count, status, ticket, def_idle, atk_idle)
+        if self.with_action_mask:
+            self._masks = self.engine.refresh_action_mask()
+        return out["reward"], out["done"], out["steps_run"]
+
     def _step(self, actions, run, partial=False):
         if self.mode == "def":
             obs, rew, done = run(def_act=actions)

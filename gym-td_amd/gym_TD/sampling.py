@@ -46,6 +46,50 @@ def _choose(cand, seed, ticket, b, j_idle, j_pick, idle):
     return int(cand[(u32(seed, ticket, b, j_pick) * n) >> 32])
 
 
+def reference_playout(env, state_of, L, cfg, hp, mode, seed, ticket, b, steps, def_idle=0, atk_idle=0, cap=True):
+    """The CPU statement of ``TDEngine.playout`` for one board: ``env`` (an oracle env of the
+    step's interface: ``step(def_act=..., atk_act=...)`` -> (obs, reward, done, info)) is played
+    on for up to ``steps`` sub-steps; sub-step j steps it with ``reference_sample`` over
+    ``reference_masks(state_of(env))`` at ticket + j (mod 2^64) under board id ``b``, and the
+    playout stops after the sub-step that ends the episode (the env is left there: a caller that
+    mirrors auto-reset resets it).  Discrete actions only.
+
+    state_of: env -> the canonical state dict ``reference_masks`` reads (with ``num_roads``).
+    Returns a dict: ``reward`` (r_0, then added left to right in f64), ``done``, ``steps_run``,
+    ``first_def`` / ``first_atk`` (sub-step 0's actions; None for a side the mode lacks),
+    ``info`` (the last sub-step's) and ``events``: per sub-step a dict with ``def`` (the action
+    index or None), ``def_n``, ``atk`` ((road, type) or None), ``atk_n`` (the candidate counts;
+    None for a side the mode lacks).
+    """
+    from .masks import reference_masks
+    A = 6 * L * L
+    total, done, info, run = 0.0, False, None, 0
+    first_def = first_atk = None
+    events = []
+    for j in range(int(steps)):
+        dm, _, am = reference_masks(state_of(env), L, cfg, hp, mode, False, cap=cap)
+        d, a, dn, an = reference_sample(dm, am, seed, (int(ticket) + j) & M64, b, def_idle, atk_idle, L, False)
+        if j == 0:
+            first_def, first_atk = d, a
+        kw = {}
+        if mode != "atk":
+            kw["def_act"] = d
+        if mode != "def":
+            kw["atk_act"] = a
+        _, r, done, info = env.step(**kw)
+        rt = None
+        if a is not None:
+            roads = np.flatnonzero(a[:, 0] != 4)
+            rt = (int(roads[0]), int(a[roads[0], 0])) if len(roads) else None
+        events.append({"def": None if d is None or d == A else int(d), "def_n": dn, "atk": rt, "atk_n": an})
+        total = float(r) if j == 0 else total + float(r)
+        run = j + 1
+        if done:
+            break
+    return {"reward": total, "done": bool(done), "steps_run": run, "first_def": first_def, "first_atk": first_atk,
+            "info": info, "events": events}
+
+
 def reference_sample(def_mask, atk_mask, seed, ticket, b, def_idle, atk_idle, L, multi):
     """(def_act, atk_act, def_count, atk_count) of board b, in the step's formats.
 

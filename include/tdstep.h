@@ -619,6 +619,85 @@ int td_sample_actions_boards_dev(td_handle* h, const td_sample_io* io, const int
  * a generic side).  The string is the handle's, valid until the next call. */
 const char* td_sample_actions_kernel_name(td_handle* h);
 
+/* Random playouts: up to `steps` board steps ("sub-steps") of every board in ONE launch, under
+ * the uniform random legal policy, with no observation written -- what a Monte-Carlo search
+ * spends its time in.  Everything is defined by calls the library already has.  Sub-step j
+ * (j = 0, 1, ...) of a board is exactly this pair:
+ *   td_sample_actions with (seed, ticket + j mod 2^64, def_idle, atk_idle) for every side the
+ *     caller controls, on the board's state before the sub-step (the key is the board id);
+ *   one td_step_boards step of that board with those actions.
+ * TD-def: the defender is sampled and the built-in attacker acts on the board's own stream;
+ * TD-atk: the attacker is sampled and the built-in defender acts; TD-2p: both sides are sampled
+ * from the same pre-state, as one td_sample_actions call gives them.
+ *   A board stops after the sub-step that ends its episode; with auto-reset its new episode
+ *     starts there (frame skip's rule: at most one staged layout per launch; a ring found dry
+ *     is waited for as in td_step, and TD_FLAG_NO_LAYOUT where no layout comes).
+ *   A board never reset gets reward 0, done 1, steps_run 0 and TD_FLAG_NO_LAYOUT, and nothing
+ *     else of it changes (win -1, allow_next 0, cooldowns 0, ep_return 0, ep_len 0; first_def
+ *     the no-op, first_atk all 4).
+ *   What is sampled is legal: a playout never sets TD_FLAG_BAD_ACTION and every sub-step's
+ *     FailCode is 0.
+ * After the call the board's exported state, the opponent's stream (td_get_py_state; for a board
+ * whose episode did not end also the raw words and the lazy-twist boundary), the flags (OR-ed),
+ * td_episode_stats and td_episode_records equal those of the loop of td_sample_actions_boards +
+ * td_step_boards over the boards not yet done.  A board's layout stream may be drawn further
+ * ahead than the loop's (refills); the layouts and their order do not differ.
+ * Outputs, each of full-batch shape and indexed by board id; only the rows of the boards played
+ * are written; reward and done are required, every other pointer may be NULL:
+ *   reward      double [B]: r_0, then the sub-steps' rewards added left to right in f64 (TD-atk:
+ *               each already negated), as frame skip
+ *   done        uint8 [B];  steps_run  int32 [B]: the sub-steps executed
+ *   win, allow_next, cooldowns, ep_return, ep_len: what the last executed sub-step would have
+ *               written (td_step_io)
+ *   first_def   int64 [B], first_atk int64 [B][3][8]: the actions sampled in sub-step 0, byte
+ *               for byte td_sample_actions' rows at `ticket` -- which move the playout began with
+ * Accounting: the call is one launch for the refill cadence and the ring guard (a board consumes
+ * at most one layout per launch) and takes the next td_kernel_timing pair, as the list calls do.
+ * It leaves the retained observation behind, as td_copy_boards with obs == NULL: the next step
+ * into the retained buffer writes every byte.  td_frame_skip() plays no part and is not changed.
+ * Asynchronous on `stream`, which must be the step's stream; nothing is waited for.
+ * Refused (< 0, a whole message in td_last_error, nothing enqueued, nothing changed), in this
+ * order: a NULL io; a bad size / abi word; a NULL handle; steps outside
+ * [1, TD_MAX_PLAYOUT_STEPS]; a missing reward or done; first_def on TD-atk or first_atk on
+ * TD-def; a multi-action handle; random_agent = 0.
+ * td_playout_boards / td_playout_boards_dev -- the boards a list names, under td_step_boards /
+ *   td_step_boards_dev's contracts word for word where they apply.  Host list: n < 0 or n > the
+ *   handle's boards, NULL boards with n > 0, an id out of range or named twice are refused on the
+ *   host; n == 0 returns 0 and launches nothing; the ids travel through the pinned id slots, so
+ *   the caller's array is free on return.  Device list: cap < 0 (with the io words, before the
+ *   handle), cap > the handle's boards and NULL boards_dev on the host; cap == 0 returns 0;
+ *   TD_LIST_BAD_COUNT, TD_LIST_RANGE, TD_LIST_TWICE on the device (td_list_check_kernel in front,
+ *   the next serial of the handle's device-list calls): then no byte of any board, stream or
+ *   output changes, the call returned 0 and td_list_errors counts it.  Boards not named keep
+ *   every byte of state, both streams, their flags, their staged layouts and their output rows. */
+#define TD_MAX_PLAYOUT_STEPS 4096
+typedef struct td_playout_io {
+  uint32_t size, abi;          /* checked first, as td_step_io / td_sample_io */
+  int32_t steps;               /* sub-steps per board, 1 .. TD_MAX_PLAYOUT_STEPS */
+  uint32_t def_idle, atk_idle; /* td_sample_io's, in units of 2^-32 */
+  uint32_t reserved;           /* 0 */
+  uint64_t seed, ticket;       /* td_sample_io's; sub-step j draws at ticket + j */
+  double* reward;
+  uint8_t* done;
+  int32_t* steps_run;
+  int8_t* win;
+  uint8_t* allow_next;
+  uint8_t* cooldowns;
+  double* ep_return;
+  int32_t* ep_len;
+  int64_t* first_def;
+  int64_t* first_atk;
+} td_playout_io;
+/* Zero *io and set its size / abi words. */
+void td_playout_io_init(td_playout_io* io);
+int td_playout(td_handle* h, const td_playout_io* io, void* stream);
+int td_playout_boards(td_handle* h, const td_playout_io* io, const int32_t* boards, int n, void* stream);
+int td_playout_boards_dev(td_handle* h, const td_playout_io* io, const int32_t* boards_dev, int cap,
+                          const int32_t* count_dev, td_list_status* status_dev, void* stream);
+/* The kernel the three calls launch, as rocprofv3 shows it: "td_playout_kernel<10, 0>" (L or 0
+ * for a generic side, mode).  The string is the handle's, valid until the next call. */
+const char* td_playout_kernel_name(td_handle* h);
+
 /* Which step kernel td_step launches (one wave per board in all three; they differ in
  * occupancy and load schedule, not in results):
  *   TD_KERNEL_LARGE  td_step_kernel        several rounds of waves (7 per SIMD), live slots
