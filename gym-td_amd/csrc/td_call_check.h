@@ -65,6 +65,51 @@ inline bool sample_io_refused(const char* fn, const SampleIoSeen& v, unsigned wa
   return true;
 }
 
+// What td_sample_weighted and its list forms refuse of their io, in this order: a NULL io, a bad
+// size / abi word, a NULL handle, no action output wanted, any pointer of a side the mode lacks, an
+// action output without its weights or a mass without its action, a weight pointer that is no
+// multiple of 4, a pitch outside [row, max_pitch] (0: the row), the defender side on a multi-action
+// handle (its attacker side is served).  The caller fills in everything behind the header words
+// only once they match and there is a handle.  row: 6 L^2 + 1 floats.
+struct SampleWIoSeen {
+  bool io = false;                // io != NULL
+  unsigned size = 0, abi = 0;     // its two header words
+  bool handle = false;            // h != NULL
+  int mode = 0, multi = 0;        // the handle's
+  bool def_act = false, atk_act = false, def_w = false, atk_w = false, def_mass = false, atk_mass = false;  // != NULL
+  bool def_w_aligned = true, atk_w_aligned = true;  // the address is a multiple of 4
+  size_t pitch = 0, row = 0;      // io->def_w_pitch; the handle's row
+};
+inline bool sample_w_io_header_ok(const SampleWIoSeen& v, unsigned want_size, int want_abi) {
+  return v.io && v.size == want_size && v.abi == (unsigned)want_abi;
+}
+inline bool sample_w_io_refused(const char* fn, const SampleWIoSeen& v, unsigned want_size, int want_abi, size_t max_pitch,
+                                char* msg, size_t n) {
+  if (!v.io) std::snprintf(msg, n, "%s: NULL io", fn);
+  else if (!sample_w_io_header_ok(v, want_size, want_abi))
+    std::snprintf(msg, n, "%s: td_sample_w_io has size %u / abi %u, this library expects size %u / abi %d "
+                  "(call td_sample_w_io_init)", fn, v.size, v.abi, want_size, want_abi);
+  else if (!v.handle) std::snprintf(msg, n, "%s: NULL handle", fn);
+  else if (!v.def_act && !v.atk_act) std::snprintf(msg, n, "%s: no action output wanted (def_act and atk_act are NULL)", fn);
+  else if ((v.def_act || v.def_w || v.def_mass) && v.mode == 1)
+    std::snprintf(msg, n, "%s: TD-atk has no defender side (def_act / def_w / def_mass)", fn);
+  else if ((v.atk_act || v.atk_w || v.atk_mass) && v.mode == 0)
+    std::snprintf(msg, n, "%s: TD-def has no attacker side (atk_act / atk_w / atk_mass)", fn);
+  else if (v.def_act && !v.def_w) std::snprintf(msg, n, "%s: def_act without its weights (def_w is NULL)", fn);
+  else if (v.atk_act && !v.atk_w) std::snprintf(msg, n, "%s: atk_act without its weights (atk_w is NULL)", fn);
+  else if (v.def_mass && !v.def_act) std::snprintf(msg, n, "%s: def_mass without its action (def_act is NULL)", fn);
+  else if (v.atk_mass && !v.atk_act) std::snprintf(msg, n, "%s: atk_mass without its action (atk_act is NULL)", fn);
+  else if (!v.def_w_aligned) std::snprintf(msg, n, "%s: def_w is no multiple of 4 (float32 rows)", fn);
+  else if (!v.atk_w_aligned) std::snprintf(msg, n, "%s: atk_w is no multiple of 4 (float32 rows)", fn);
+  else if (v.def_act && v.pitch != 0 && (v.pitch < v.row || v.pitch > max_pitch))
+    std::snprintf(msg, n, "%s: def_w_pitch %zu outside [%zu, %zu] (6 L^2 + 1 floats per row)", fn, v.pitch, v.row, max_pitch);
+  else if (v.def_act && v.multi)
+    std::snprintf(msg, n, "%s: the defender side is not supported with multi-action (one discrete action is "
+                  "sampled); the attacker side is", fn);
+  else return false;
+  return true;
+}
+
 // What td_playout and its list forms refuse of their io and of the handle's settings, in this
 // order: a NULL io, a bad size / abi word, a NULL handle, steps outside [1, max_steps], a missing
 // reward or done, a first action for a side the mode lacks, a multi-action handle, random_agent

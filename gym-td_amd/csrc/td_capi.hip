@@ -90,7 +90,7 @@ constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw doe
 constexpr int kIdSlots = 4;      // td_copy_boards, td_step_boards: id uploads in flight before a call waits for the oldest
 // The strings the kernel-name accessors hand out: one slot each, so a name stays valid until
 // its own accessor is called again (kept_name).
-enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_PLAYOUT, NAME_SLOTS };
+enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_PLAYOUT, NAME_SAMPLE_W, NAME_SLOTS };
 
 }  // namespace
 
@@ -101,7 +101,7 @@ struct td_handle {
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
-  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name, td_playout_kernel_name
+  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name, td_playout_kernel_name, td_sample_weighted_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -603,7 +603,7 @@ int create_setup(td_handle* h) {
   return td_seed(h, seeds.data(), seeds.data());
 }
 
-// td_step_io_init, td_mask_io_init, td_sample_io_init: all zero but the two header words.
+// td_step_io_init, td_mask_io_init, td_sample_io_init, td_sample_w_io_init: all zero but the two header words.
 template <class IO>
 void io_init(IO* io) {
   if (!io) return;
@@ -1290,6 +1290,63 @@ const char* td_sample_actions_kernel_name(td_handle* h) {
   char buf[64];
   std::snprintf(buf, sizeof buf, "td_sample_kernel<%d>", with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
   return kept_name(h, NAME_SAMPLE, buf);
+}
+
+void td_sample_w_io_init(td_sample_w_io* io) { io_init(io); }
+
+namespace {
+
+// What td_sample_weighted and its list forms check of their io (td_call_check.h
+// sample_w_io_refused), and the kernel arguments they make of it.  fn: the caller's name.
+int check_sample_w_io(const char* fn, const td_handle* h, const td_sample_w_io* io, SampleWArgs* out) {
+  SampleWIoSeen v;
+  v.io = io != nullptr;
+  if (io) { v.size = io->size; v.abi = io->abi; }
+  v.handle = h != nullptr;
+  if (sample_w_io_header_ok(v, (unsigned)sizeof(td_sample_w_io), TD_ABI_VERSION) && h) {
+    v.mode = h->mode; v.multi = h->multi;
+    v.def_act = io->def_act; v.atk_act = io->atk_act; v.def_w = io->def_w; v.atk_w = io->atk_w;
+    v.def_mass = io->def_mass; v.atk_mass = io->atk_mass;
+    v.def_w_aligned = (reinterpret_cast<uintptr_t>(io->def_w) & 3u) == 0;
+    v.atk_w_aligned = (reinterpret_cast<uintptr_t>(io->atk_w) & 3u) == 0;
+    v.pitch = io->def_w_pitch;
+    v.row = (size_t)6 * h->NC + 1;
+  }
+  char msg[240];
+  if (sample_w_io_refused(fn, v, (unsigned)sizeof(td_sample_w_io), TD_ABI_VERSION, kSampleWMaxPitch, msg, sizeof msg))
+    return fail("%s", msg);
+  *out = {board_view(h), io->def_act, io->atk_act, io->def_w, io->atk_w, io->def_mass, io->atk_mass,
+          io->def_w_pitch ? io->def_w_pitch : v.row, sample_key(io->seed, io->ticket)};
+  return 0;
+}
+
+}  // namespace
+
+// td_sample_actions' three forms with the weighted kernel: one kernel on the caller's stream,
+// nothing waited for, state only read.
+int td_sample_weighted(td_handle* h, const td_sample_w_io* io, void* stream) {
+  SampleWArgs a;
+  if (check_sample_w_io("td_sample_weighted", h, io, &a)) return -1;
+  HIP_OK(launch_sample_weighted(a, nullptr, h->B, nullptr, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+int td_sample_weighted_boards(td_handle* h, const td_sample_w_io* io, const int32_t* boards, int n, void* stream) {
+  return read_boards("td_sample_weighted_boards", check_sample_w_io, launch_sample_weighted, h, io, boards, n, stream);
+}
+
+int td_sample_weighted_boards_dev(td_handle* h, const td_sample_w_io* io, const int32_t* boards_dev, int cap,
+                                  const int32_t* count_dev, td_list_status* status_dev, void* stream) {
+  return read_boards_dev("td_sample_weighted_boards_dev", check_sample_w_io, launch_sample_weighted, h, io, boards_dev, cap,
+                         count_dev, status_dev, stream);
+}
+
+const char* td_sample_weighted_kernel_name(td_handle* h) {
+  if (!h) return "";
+  char buf[64];
+  std::snprintf(buf, sizeof buf, "td_sample_weighted_kernel<%d>",
+                with_side(h->L, [](auto lt) { return (int)decltype(lt)::value; }));
+  return kept_name(h, NAME_SAMPLE_W, buf);
 }
 
 void td_playout_io_init(td_playout_io* io) { io_init(io); }

@@ -235,6 +235,27 @@ constexpr int kSampleWaves = 4;  // entries (waves) per workgroup, as kMaskListW
 hipError_t launch_sample(const SampleArgs& a, const int32_t* ids, int cap, const int32_t* count,
                          const td_list_status* verdict, hipStream_t s);
 
+// One legal action per side and board drawn in proportion to the caller's weights
+// (td_sample_weighted[_boards[_dev]]; td_sample_w.hip): reads the view and the weight rows, writes
+// only the outputs.  Discrete defender actions only (the call refuses the rest).
+struct SampleWArgs {
+  BoardView v;
+  int64_t* def_act;      // [B] or nullptr
+  int64_t* atk_act;      // [B][3][8] or nullptr
+  const float* def_w;    // [B][def_pitch] floats, 4-B aligned; there where def_act is
+  const float* atk_w;    // [B][13]; there where atk_act is
+  uint64_t* def_mass;    // [B][2] (m(chosen), S) or nullptr
+  uint64_t* atk_mass;    // [B][2] or nullptr
+  size_t def_pitch;      // floats per board: >= 6 L^2 + 1
+  uint64_t key;          // sample_key(seed, ticket) (td_sample.h)
+};
+static_assert(offsetof(SampleWArgs, v) == 0 && offsetof(SampleWArgs, def_act) == 48 && offsetof(SampleWArgs, key) == 104 &&
+                  sizeof(SampleWArgs) == 112, "SampleWArgs' layout");
+constexpr size_t kSampleWMaxPitch = 1u << 16;  // floats
+// ids, cap, count, verdict: launch_sample's.  kSampleWaves entries per workgroup.
+hipError_t launch_sample_weighted(const SampleWArgs& a, const int32_t* ids, int cap, const int32_t* count,
+                                  const td_list_status* verdict, hipStream_t s);
+
 // Staged layouts per board: sixteen episodes of slack for the side refills, and the
 // ring guard (td_refill_kernel) needs to run only every NSLOT - 1 steps.  (NSLOT = 4 with
 // a guard every 3rd step: +4 % / +7-9 % per step at 8,192 / 4,096 boards, profiles/r03/s13.)

@@ -89,6 +89,19 @@ class TdSampleIO(ctypes.Structure):
         super().__init__(**kw)
 
 
+class TdSampleWIO(ctypes.Structure):
+    """struct td_sample_w_io (tdstep.h): the size / ABI header, the device outputs, the weight rows,
+    the masses, the defender rows' pitch in floats, seed and ticket."""
+    _fields_ = [("size", ctypes.c_uint32), ("abi", ctypes.c_uint32), ("def_act", c_vp), ("atk_act", c_vp),
+                ("def_w", c_vp), ("atk_w", c_vp), ("def_mass", c_vp), ("atk_mass", c_vp),
+                ("def_w_pitch", ctypes.c_size_t), ("seed", ctypes.c_uint64), ("ticket", ctypes.c_uint64)]
+
+    def __init__(self, **kw):
+        kw.setdefault("size", ctypes.sizeof(TdSampleWIO))
+        kw.setdefault("abi", ABI_VERSION)
+        super().__init__(**kw)
+
+
 class TdPlayoutIO(ctypes.Structure):
     """struct td_playout_io (tdstep.h): the size / ABI header, the sub-steps, the sampler's idle
     probabilities, seed and ticket, then the device outputs."""
@@ -150,6 +163,12 @@ def _load():
         "td_sample_actions_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleIO), c_vp, ctypes.c_int, c_vp, c_vp,
                                                         c_vp]),
         "td_sample_actions_kernel_name": (ctypes.c_char_p, [c_vp]),
+        "td_sample_w_io_init": (None, [ctypes.POINTER(TdSampleWIO)]),
+        "td_sample_weighted": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleWIO), c_vp]),
+        "td_sample_weighted_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleWIO), c_vp, ctypes.c_int, c_vp]),
+        "td_sample_weighted_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdSampleWIO), c_vp, ctypes.c_int, c_vp, c_vp,
+                                                         c_vp]),
+        "td_sample_weighted_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_playout_io_init": (None, [ctypes.POINTER(TdPlayoutIO)]),
         "td_playout": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp]),
         "td_playout_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp, ctypes.c_int, c_vp]),

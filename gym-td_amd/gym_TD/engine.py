@@ -747,6 +747,125 @@ class TDEngine(object):
         'td_sample_kernel<10>'."""
         return _lib.lib.td_sample_actions_kernel_name(self._h).decode()
 
+    def _sample_weighted_prepare(self, def_w, atk_w, ticket, mass):
+        """The weights checked, and the engine's sample buffers (``sample_actions``' own, and the
+        masses allocated on first use) as a td_sample_w_io for this call's ticket."""
+        B, L = self.B, self.L
+        A1 = 6 * L * L + 1
+
+        def weights(w, name, cols, strided):
+            if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.device != self.device:
+                raise ValueError("%s must be a float32 tensor on %s, not %r" % (
+                    name, self.device, (w.dtype, w.device) if isinstance(w, torch.Tensor) else type(w)))
+            if tuple(w.shape) != (B, cols):
+                raise ValueError("%s must have shape (%d, %d), not %r" % (name, B, cols, tuple(w.shape)))
+            if w.stride(1) != 1 or (w.stride(0) != cols if not strided else not cols <= w.stride(0) <= 65536):
+                raise ValueError("%s must be contiguous in its last dimension%s, not strides %r" % (
+                    name, " with a row pitch in [%d, 65536] floats" % cols if strided else " and its rows packed", w.stride()))
+            return w
+
+        if self.multi and (self.mode == "def" or def_w is not None):
+            raise ValueError("sample_weighted: the defender side is not supported with multi-action")
+        want = {"def": self.mode != "atk" and not self.multi, "atk": self.mode != "def"}
+        given = {"def": def_w, "atk": atk_w}
+        for side in ("def", "atk"):
+            if given[side] is None and want[side]:
+                raise ValueError("sample_weighted: %s_w is required in mode %r" % (side, self.mode))
+            if given[side] is not None and not want[side]:
+                raise ValueError("sample_weighted: mode %r has no %s side (%s_w)" % (
+                    self.mode, "defender" if side == "def" else "attacker", side))
+        if want["def"]:
+            weights(def_w, "def_w", A1, True)
+        if want["atk"]:
+            weights(atk_w, "atk_w", 13, False)
+        self._sample_prepare(0, 0.0, 0.0, False)  # (the buffers; takes no ticket)
+        buf = self._sample_buf
+        if mass:
+            for side in ("def", "atk"):
+                if want[side] and buf.get(side + "_mass") is None:
+                    buf[side + "_mass"] = torch.zeros((B, 2), dtype=torch.int64, device=self.device)
+        if ticket is None:
+            ticket = self._sample_ticket
+            self._sample_ticket = (ticket + 1) & sampling.M64
+        io = _lib.TdSampleWIO(seed=self.sample_seed, ticket=int(ticket) & sampling.M64)
+        out = {"def": None, "atk": None}
+        if mass:
+            out["def_mass"] = out["atk_mass"] = None
+        for side in ("def", "atk"):
+            if not want[side]:
+                continue
+            setattr(io, side + "_act", buf[side].data_ptr())
+            setattr(io, side + "_w", given[side].data_ptr())
+            out[side] = buf[side]
+            if mass:
+                setattr(io, side + "_mass", buf[side + "_mass"].data_ptr())
+                out[side + "_mass"] = buf[side + "_mass"]
+        if want["def"]:
+            io.def_w_pitch = int(def_w.stride(0))
+        self._keep_sample_weights = (def_w, atk_w)  # alive until the next call's kernel is behind them on the stream
+        return io, out
+
+    def sample_weighted(self, def_w=None, atk_w=None, ticket=None, mass=False):
+        """One legal action per side and board drawn in proportion to the caller's weights, on
+        the device (td_sample_weighted): what ``action_mask()`` + ``w * mask`` +
+        ``torch.multinomial`` + a scatter would give, in one kernel and in the formats ``step()``
+        takes -- a policy network's action distribution, PUCT priors, a heuristic prior.
+
+        ``def_w``: float32 device tensor (B, 6 L^2 + 1), the no-op last (a view with strides
+        (pitch, 1), pitch <= 65,536 floats, is taken as it is); ``atk_w``: float32 (B, 13), entry
+        road * 4 + type and "summon nothing" last.  Weights are meant in [0, 1] -- probabilities,
+        or ``gym_TD.sampling.weights_from_logits(logits)`` --, quantised to multiples of 2^-31
+        (values above 1 count as 1; NaN, negatives and values below 2^-31 as 0) and summed as
+        integers over the legal entries: the result equals
+        ``gym_TD.sampling.reference_sample_weighted`` bit for bit.  Nothing legal with weight:
+        the no-op.  Idling is the no-op's own weight: there is no idle probability.  Each side
+        the mode has needs its weights; multi-action defenders are not supported.
+
+        Returns a dict of the engine's own device tensors, the ones ``sample_actions`` writes
+        (``step_boards(..., eng._sample_buf)`` keeps working): ``"def"`` int64 (B,), ``"atk"``
+        int64 (B, 3, 8), and with ``mass`` ``"def_mass"`` / ``"atk_mass"`` int64 (B, 2) =
+        (m(chosen), S), (0, 0) where S == 0: the pick's log-probability is log m - log S.  A side
+        the mode lacks is None.  ``sample_seed`` and the ticket counter are ``sample_actions``'
+        (a weighted and a uniform call at one ticket share random words: leave ``ticket=None``
+        or vary it).  No board, stream or flag changes; one kernel on torch's current stream,
+        which must be the stream of step()."""
+        io, out = self._sample_weighted_prepare(def_w, atk_w, ticket, mass)
+        _lib.check(_lib.lib.td_sample_weighted(self._h, io, self._stream()))
+        return out
+
+    def sample_weighted_boards(self, boards, def_w=None, atk_w=None, ticket=None, mass=False):
+        """``sample_weighted`` for the boards named in ``boards`` only (td_sample_weighted_boards),
+        the partner of ``step_boards``: every tensor, the weights included, keeps its full-batch
+        shape and is indexed by board id, only the named rows are written, and a named board's
+        row is the one ``sample_weighted`` gives it under the same ticket.  ``boards`` under
+        ``step_boards``' rules; TDError, nothing written: an id out of range or named twice."""
+        ids = _board_ids(boards)
+        io, out = self._sample_weighted_prepare(def_w, atk_w, ticket, mass)
+        _lib.check(_lib.lib.td_sample_weighted_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()))
+        return out
+
+    def sample_weighted_boards_dev(self, boards, count=None, status=None, def_w=None, atk_w=None, ticket=None,
+                                   mass=False):
+        """``sample_weighted_boards`` for ids that are on the device
+        (td_sample_weighted_boards_dev), the partner of ``step_boards_dev``: nothing is copied
+        to the host or waited for.  ``boards``, ``count`` and ``status`` as in
+        ``step_boards_dev``; a list the device refuses writes no byte (``list_errors()``).  The
+        tensors stay alive until the next call."""
+        ids = _dev_ids(boards, self.device, "sample_weighted_boards")
+        c = _dev_words(count, 1, self.device, "count")
+        st = _dev_words(status, 4, self.device, "status")
+        io, out = self._sample_weighted_prepare(def_w, atk_w, ticket, mass)
+        _lib.check(_lib.lib.td_sample_weighted_boards_dev(self._h, io, ids.data_ptr(), int(ids.numel()),
+                                                          c.data_ptr() if c is not None else None,
+                                                          st.data_ptr() if st is not None else None, self._stream()))
+        self._keep_sample_list = (ids, c, st)  # alive until the next call's kernels are behind them on the stream
+        return out
+
+    def sample_weighted_kernel_name(self):
+        """The kernel the three weighted sampling calls launch (td_sample_weighted_kernel_name),
+        e.g. 'td_sample_weighted_kernel<10>'."""
+        return _lib.lib.td_sample_weighted_kernel_name(self._h).decode()
+
     # ---------------------------------------------------------------- playouts
     def _playout_prepare(self, steps, ticket, def_idle, atk_idle, first):
         """The engine's playout buffers (allocated on first use) as a td_playout_io for this

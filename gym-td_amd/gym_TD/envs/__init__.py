@@ -438,6 +438,24 @@ class TDVecEnv(object):
         search iteration -- fork, sample, step -- without a host round trip."""
         return self._sampled(self.engine.sample_actions_boards_dev(boards, count, status, ticket, def_idle, atk_idle))
 
+    def sample_weighted(self, def_w=None, atk_w=None, ticket=None):
+        """One legal action per env drawn in proportion to the caller's weights, on the device
+        (TDEngine.sample_weighted), as step() takes it for the mode: ``def_w`` float32
+        (num_envs, 6 L^2 + 1), ``atk_w`` float32 (num_envs, 13), each where the mode has the side.
+        The masses, for log-probabilities: ``engine.sample_weighted(..., mass=True)``."""
+        return self._sampled(self.engine.sample_weighted(def_w, atk_w, ticket))
+
+    def sample_weighted_boards(self, boards, def_w=None, atk_w=None, ticket=None):
+        """sample_weighted() for the envs named in ``boards`` only
+        (TDEngine.sample_weighted_boards), the partner of step_boards(): full-batch tensors,
+        weights included, the named rows fresh."""
+        return self._sampled(self.engine.sample_weighted_boards(boards, def_w, atk_w, ticket))
+
+    def sample_weighted_boards_dev(self, boards, count=None, status=None, def_w=None, atk_w=None, ticket=None):
+        """sample_weighted_boards() for env ids that are on the device
+        (TDEngine.sample_weighted_boards_dev), the partner of step_boards_dev()."""
+        return self._sampled(self.engine.sample_weighted_boards_dev(boards, count, status, def_w, atk_w, ticket))
+
     def playout(self, steps, boards=None, ticket=None, def_idle=0.0, atk_idle=0.0):
         """Random playouts of every env, or of the envs named in ``boards``
         (TDEngine.playout): up to ``steps`` board steps under the uniform random legal policy in

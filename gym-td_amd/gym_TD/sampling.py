@@ -1,7 +1,10 @@
-"""Uniform legal-action sampling restated in numpy: the reference of ``TDEngine.sample_actions``.
+"""Legal-action sampling restated in numpy: the reference of ``TDEngine.sample_actions`` and of
+``TDEngine.sample_weighted``.
 
-The rule of csrc/td_sample.h -- splitmix64 over (seed, ticket, board id, draw), an idle draw and
-a multiply-shift pick per side -- applied to the masks of ``gym_TD.masks.reference_masks``.
+The rules of csrc/td_sample.h -- splitmix64 over (seed, ticket, board id, draw); uniform: an idle
+draw and a multiply-shift pick per side; weighted: float32 weights quantised to integers, an
+integer total and a 64-bit multiply-shift threshold against the prefix sums -- applied to the
+masks of ``gym_TD.masks.reference_masks``.
 """
 import numpy as np
 
@@ -119,3 +122,71 @@ def reference_sample(def_mask, atk_mask, seed, ticket, b, def_idle, atk_idle, L,
         if k is not None:
             a_act[k // 4, 0] = k % 4
     return d_act, a_act, d_n, a_n
+
+
+def quantize(w):
+    """q of td_sample_weighted, elementwise: 0 unless w > 0 (NaN, -0, negatives, 0), else
+    trunc(min(w, 1) * 2^31) with the product taken in float32 (exact: a power of two).  +inf and
+    everything above 1 give 2^31; subnormals and everything below 2^-31 give 0.  ``w`` is taken as
+    float32; returns int64 of the same shape."""
+    w = np.asarray(w, dtype=np.float32)
+    pos = w > 0  # (False for NaN)
+    c = np.where(pos, np.minimum(np.where(pos, w, np.float32(0)), np.float32(1)), np.float32(0)).astype(np.float32)
+    return (c * np.float32(2.0 ** 31)).astype(np.float32).astype(np.int64)
+
+
+def weights_from_logits(logits):
+    """exp(l - row max) in float32 over the last axis: weights in (0, 1] whose row maximum is
+    exactly 1, as ``sample_weighted`` takes them.  A torch tensor gives a torch tensor (on its
+    device), anything else a numpy array."""
+    try:
+        import torch
+    except ImportError:  # (the reference alone needs numpy only)
+        torch = None
+    if torch is not None and isinstance(logits, torch.Tensor):
+        x = logits.to(torch.float32)
+        return torch.exp(x - x.max(dim=-1, keepdim=True).values)
+    x = np.asarray(logits, dtype=np.float32)
+    return np.exp(x - x.max(axis=-1, keepdims=True)).astype(np.float32)
+
+
+def pick_weighted(m, w64):
+    """The rule over the masses ``m`` (ints, 0 where illegal, the always-legal entry last) and the
+    draw's 64-bit word: (pick, (m(pick), S)), or (the last entry, (0, 0)) when S == 0."""
+    m = [int(x) for x in m]
+    S = sum(m)
+    if S == 0:
+        return len(m) - 1, (0, 0)
+    r = (int(w64) * S) >> 64
+    c = 0
+    for e, x in enumerate(m):
+        c += x
+        if c > r:
+            return e, (x, S)
+    raise AssertionError("r < S")
+
+
+def reference_sample_weighted(def_mask, atk_mask, def_w, atk_w, seed, ticket, b, L):
+    """(def_act, atk_act, def_mass, atk_mass) of board b under td_sample_weighted's rule.
+
+    def_mask: reference_masks' discrete row (6 L^2 + 1,), or None (TD-atk); atk_mask: (3, 5) or
+    None (TD-def).  def_w: the board's (6 L^2 + 1,) float32 weights, the no-op last; atk_w: its
+    (13,) weights, entry road * 4 + t and "nothing" last.  def_act: int (6 L^2 = the no-op);
+    atk_act: int64 (3, 8), all 4 but the chosen road's first slot; the masses: (m(chosen), S) as
+    ints, (0, 0) when S == 0.  A side without a mask gives None for its action and its mass.
+    """
+    A = 6 * L * L
+    d_act = a_act = d_mass = a_mass = None
+    if def_mask is not None:
+        legal = np.asarray(def_mask).reshape(-1)[:A + 1] != 0
+        legal[A] = True  # the no-op
+        m = np.where(legal, quantize(np.asarray(def_w, dtype=np.float32).reshape(-1)[:A + 1]), 0)
+        d_act, d_mass = pick_weighted(m, word(seed, ticket, b, DEF_PICK))
+    if atk_mask is not None:
+        legal = np.append(np.asarray(atk_mask)[:, :4].reshape(-1) != 0, True)  # road * 4 + t, then "nothing"
+        m = np.where(legal, quantize(np.asarray(atk_w, dtype=np.float32).reshape(-1)[:13]), 0)
+        e, a_mass = pick_weighted(m, word(seed, ticket, b, ATK_PICK))
+        a_act = np.full((3, 8), 4, dtype=np.int64)
+        if e < 12:
+            a_act[e // 4, 0] = e % 4
+    return d_act, a_act, d_mass, a_mass

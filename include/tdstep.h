@@ -619,6 +619,80 @@ int td_sample_actions_boards_dev(td_handle* h, const td_sample_io* io, const int
  * a generic side).  The string is the handle's, valid until the next call. */
 const char* td_sample_actions_kernel_name(td_handle* h);
 
+/* One legal action per side and board drawn in proportion to caller-supplied weights, on the
+ * device: the link between a policy's output tensor (a network's action distribution, PUCT
+ * priors, a heuristic prior) and td_step, where td_sample_actions serves the uniform policy.
+ * The rule is exact -- integers only, so the result does not depend on how the sum is taken:
+ *   weights  float32, meant in [0, 1]: probabilities, or exp(logit - row max)
+ *   q(w)     0 unless w > 0 (NaN, -0, negatives and 0 give 0), else
+ *            (uint32) trunc(min(w, 1.0f) * 2^31): +inf and everything above 1 give 2^31,
+ *            subnormals and everything below 2^-31 give 0
+ *   defender, discrete handles only: entries a in [0, 6 L^2]; m(a) = q(def_w[b][a]) where a is
+ *            6 L^2 (the no-op, always legal) or a candidate of td_sample_actions
+ *            (td_action_mask's def_mask[a] == 1), else 0.  S = sum of m(a), a uint64 < 2^44.
+ *            S == 0: the no-op.  Else r = (word(seed, ticket, b, 1) * S) >> 64 -- the whole
+ *            64-bit word of td_sample_actions' draw j = 1, a 64 x 64 -> 128-bit product -- and
+ *            the action is the smallest a whose inclusive prefix sum of m exceeds r.
+ *   attacker entries e in [0, 12]: e < 12 is the pair (road, t) = (e >> 2, e & 3), legal iff
+ *            atk_mask[road][t] == 1; e = 12 is "summon nothing", always legal.  Weights
+ *            atk_w[b][13], draw j = 3, the same rule.  The output [3][8] is all 4 but the chosen
+ *            road's first slot, as td_sample_actions writes it.
+ *   mass     on request, per side: uint64 [B][2] = (m(chosen), S), or (0, 0) when S == 0.  The
+ *            pick's probability is m / S, up to a multiply-shift bias of at most S / 2^64 < 2^-20
+ *            (log-probability: log m - log S).
+ * Idling is part of the distribution (the no-op's weight, entry 12): there is no def_idle /
+ * atk_idle, and draws 0 and 2 are unused.  The key is td_sample_actions': the board id, not the
+ * list position -- a weighted and a uniform call at the same (seed, ticket) share words: vary
+ * `ticket` per call.  One candidate per side, so the step executes what was sampled: RealAction
+ * is the sampled action and FailCode 0.  While the defender's cool-down is closed, and on a
+ * board never reset, only the always-legal entry can carry mass: the result is the no-op and the
+ * weight row is not read (but its last float, for the mass).  A call writes nothing but its
+ * outputs -- no board, RNG stream, flag, ledger or refill cadence changes.
+ *   def_act    int64 [B]; NULL = not wanted        atk_act   int64 [B][3][8]; NULL = not wanted
+ *   def_w      float32 [B][def_w_pitch], entry a of board b at def_w[b * def_w_pitch + a]
+ *   atk_w      float32 [B][13]
+ *   def_mass, atk_mass   uint64 [B][2]; may be NULL
+ *   def_w_pitch  floats between rows; 0 = 6 L^2 + 1, else >= 6 L^2 + 1 and <= 65,536
+ * The weight pointers need 4-byte alignment only; the result is the same at any alignment of the
+ * rows, and nothing behind a row's 6 L^2 + 1 (13) floats is read.
+ * Refused (< 0, nothing launched), in this order: a NULL io, a bad size / abi word, a NULL
+ * handle, no action output wanted, any pointer of a side the mode lacks, an action output
+ * without its weights or a mass without its action, a weight pointer that is no multiple of 4, a
+ * bad pitch, the defender side on a multi-action handle (the attacker side of such a handle is
+ * served).  Asynchronous on `stream`, which must be the step's stream; nothing is waited for.
+ * The calls take no td_kernel_timing pair and are no launch for the refill cadence.
+ * td_sample_weighted_boards / _boards_dev -- the list forms, under
+ *   td_sample_actions_boards[_dev]'s contract word for word: the arrays, weights included, keep
+ *   their full-batch shape and are indexed by board id, only the named rows are written, and the
+ *   row of a named board is the row td_sample_weighted gives that board under the same seed and
+ *   ticket.  Host list: n < 0 or n > the handle's boards, NULL boards with n > 0, an id out of
+ *   range or named twice are refused on the host; n == 0 returns 0.  Device list: cap < 0 (with
+ *   the io words, before the handle), cap > the handle's boards and NULL boards_dev on the host;
+ *   TD_LIST_BAD_COUNT, TD_LIST_RANGE, TD_LIST_TWICE on the device (td_list_check_kernel in
+ *   front, the next serial of the handle's device-list calls): then no output byte is written,
+ *   the call returned 0 and td_list_errors counts it.  td_frame_skip() > 1 and random_agent = 0
+ *   are no reason to refuse. */
+typedef struct td_sample_w_io {
+  uint32_t size, abi;          /* checked first, as td_step_io / td_sample_io */
+  int64_t* def_act;
+  int64_t* atk_act;
+  const float* def_w;
+  const float* atk_w;
+  uint64_t* def_mass;
+  uint64_t* atk_mass;
+  size_t def_w_pitch;
+  uint64_t seed, ticket;
+} td_sample_w_io;
+/* Zero *io and set its size / abi words. */
+void td_sample_w_io_init(td_sample_w_io* io);
+int td_sample_weighted(td_handle* h, const td_sample_w_io* io, void* stream);
+int td_sample_weighted_boards(td_handle* h, const td_sample_w_io* io, const int32_t* boards, int n, void* stream);
+int td_sample_weighted_boards_dev(td_handle* h, const td_sample_w_io* io, const int32_t* boards_dev, int cap,
+                                  const int32_t* count_dev, td_list_status* status_dev, void* stream);
+/* The kernel the three calls launch, as rocprofv3 shows it: "td_sample_weighted_kernel<10>" (L,
+ * or 0 for a generic side).  The string is the handle's, valid until the next call. */
+const char* td_sample_weighted_kernel_name(td_handle* h);
+
 /* Random playouts: up to `steps` board steps ("sub-steps") of every board in ONE launch, under
  * the uniform random legal policy, with no observation written -- what a Monte-Carlo search
  * spends its time in.  Everything is defined by calls the library already has.  Sub-step j
