@@ -115,6 +115,8 @@ inline bool sample_w_io_refused(const char* fn, const SampleWIoSeen& v, unsigned
 // reward or done, a first action for a side the mode lacks, a multi-action handle, random_agent
 // = 0.  The caller fills in everything behind the header words only once they match, and the
 // handle's settings only where there is a handle.  mode: 0 TD-def, 1 TD-atk, 2 TD-2p.
+// td_probe and its list forms refuse the same in the same order, with reps outside [1, max_reps]
+// behind the steps: `probe` names the io and the limit (nullptr: the playout's io, no replicas).
 struct PlayoutIoSeen {
   bool io = false;                // io != NULL
   unsigned size = 0, abi = 0;     // its two header words
@@ -122,25 +124,33 @@ struct PlayoutIoSeen {
   int steps = 0;                  // io->steps
   bool reward = false, done = false, first_def = false, first_atk = false;  // != NULL
   int mode = 0, multi = 0, opp_np = 0;  // the handle's
+  int reps = 1;                   // io->reps (a probe's)
+};
+struct ProbeIoLimit {
+  int max_reps;  // TD_MAX_PROBE_REPS
 };
 inline bool playout_io_header_ok(const PlayoutIoSeen& v, unsigned want_size, int want_abi) {
   return v.io && v.size == want_size && v.abi == (unsigned)want_abi;
 }
 inline bool playout_io_refused(const char* fn, const PlayoutIoSeen& v, unsigned want_size, int want_abi, int max_steps,
-                               char* msg, size_t n) {
+                               char* msg, size_t n, const ProbeIoLimit* probe = nullptr) {
+  const char* const io = probe ? "td_probe_io" : "td_playout_io";
+  const char* const what = probe ? "probe" : "playout";
   if (!v.io) std::snprintf(msg, n, "%s: NULL io", fn);
   else if (!playout_io_header_ok(v, want_size, want_abi))
-    std::snprintf(msg, n, "%s: td_playout_io has size %u / abi %u, this library expects size %u / abi %d "
-                  "(call td_playout_io_init)", fn, v.size, v.abi, want_size, want_abi);
+    std::snprintf(msg, n, "%s: %s has size %u / abi %u, this library expects size %u / abi %d "
+                  "(call %s_init)", fn, io, v.size, v.abi, want_size, want_abi, io);
   else if (!v.handle) std::snprintf(msg, n, "%s: NULL handle", fn);
   else if (v.steps < 1 || v.steps > max_steps)
     std::snprintf(msg, n, "%s: steps = %d outside [1, %d] (TD_MAX_PLAYOUT_STEPS)", fn, v.steps, max_steps);
+  else if (probe && (v.reps < 1 || v.reps > probe->max_reps))
+    std::snprintf(msg, n, "%s: reps = %d outside [1, %d] (TD_MAX_PROBE_REPS)", fn, v.reps, probe->max_reps);
   else if (!v.reward || !v.done) std::snprintf(msg, n, "%s: reward and done are required", fn);
   else if (v.first_def && v.mode == 1) std::snprintf(msg, n, "%s: TD-atk has no defender side (first_def)", fn);
   else if (v.first_atk && v.mode == 0) std::snprintf(msg, n, "%s: TD-def has no attacker side (first_atk)", fn);
   else if (v.multi)
-    std::snprintf(msg, n, "%s: not supported with multi-action (the playout samples one discrete action per side and "
-                  "sub-step)", fn);
+    std::snprintf(msg, n, "%s: not supported with multi-action (the %s samples one discrete action per side and "
+                  "sub-step)", fn, what);
   else if (v.opp_np)
     std::snprintf(msg, n, "%s: not supported with random_agent = 0 (the built-in opponent would draw from the layout "
                   "stream inside the launch)", fn);

@@ -90,7 +90,7 @@ constexpr int kSideStreams = 2;  // refill streams: one stuck on a long draw doe
 constexpr int kIdSlots = 4;      // td_copy_boards, td_step_boards: id uploads in flight before a call waits for the oldest
 // The strings the kernel-name accessors hand out: one slot each, so a name stays valid until
 // its own accessor is called again (kept_name).
-enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_PLAYOUT, NAME_SAMPLE_W, NAME_SLOTS };
+enum { NAME_STEP, NAME_SEL, NAME_LIST, NAME_MASK_LIST, NAME_SAMPLE, NAME_PLAYOUT, NAME_SAMPLE_W, NAME_PROBE, NAME_SLOTS };
 
 }  // namespace
 
@@ -101,7 +101,7 @@ struct td_handle {
   int resident[2][2] = {};    // [format][waves - 1]: boards resident at once (step_resident_boards)
   int obs_fmt = TD_OBS_F32;   // td_set_obs_format: the element every obs pointer is taken to hold
   int frame_skip = 1;         // td_set_frame_skip: board steps per td_step (> 1: the skip kernel is launched)
-  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name, td_playout_kernel_name, td_sample_weighted_kernel_name
+  std::string names[NAME_SLOTS];  // td_step_kernel_name, td_step_boards[_dev]_kernel_name, td_action_mask_boards_kernel_name, td_sample_actions_kernel_name, td_playout_kernel_name, td_sample_weighted_kernel_name, td_probe_kernel_name
   int lw = 0;  // layout record words
   size_t scratch_stride = 0;
   TdDevCfg dcfg;
@@ -1447,6 +1447,89 @@ const char* td_playout_kernel_name(td_handle* h) {
   StepArgs a = base_args(h);
   a.multi = 0;  // (a multi-action handle is refused: the discrete row's name)
   return kept_name(h, NAME_PLAYOUT, kernel_display_name(playout_row(a)));
+}
+
+void td_probe_io_init(td_probe_io* io) { io_init(io); }
+
+namespace {
+
+// What a probe's launch needs: the handle (for the timing pair only), the step arguments with the
+// io's outputs, and the probe's own.  The list is filled in at the launch.
+struct ProbeCall {
+  td_handle* h;
+  StepArgs a;
+  ProbeArgs q;
+};
+
+// What td_probe and its list forms check of their io and of the handle's settings: the playout's
+// refusals with the replicas behind the steps (td_call_check.h playout_io_refused), and the call
+// they make of it.  fn: the caller's name.
+int check_probe_io(const char* fn, td_handle* h, const td_probe_io* io, ProbeCall* out) {
+  PlayoutIoSeen v;
+  v.io = io != nullptr;
+  if (io) { v.size = io->size; v.abi = io->abi; }
+  v.handle = h != nullptr;
+  if (playout_io_header_ok(v, (unsigned)sizeof(td_probe_io), TD_ABI_VERSION)) {
+    v.steps = io->steps; v.reps = io->reps;
+    v.reward = io->reward; v.done = io->done; v.first_def = io->first_def; v.first_atk = io->first_atk;
+    if (h) { v.mode = h->mode; v.multi = h->multi; v.opp_np = h->opp_np; }
+  }
+  char msg[240];
+  const ProbeIoLimit lim{TD_MAX_PROBE_REPS};
+  if (playout_io_refused(fn, v, (unsigned)sizeof(td_probe_io), TD_ABI_VERSION, TD_MAX_PLAYOUT_STEPS, msg, sizeof msg, &lim))
+    return fail("%s", msg);
+  out->h = h;
+  StepArgs& a = out->a;
+  a = base_args(h);
+  a.frame_skip = io->steps;  // the sub-steps of a replica; td_frame_skip() plays no part
+  a.reward = io->reward; a.done = io->done; a.win = io->win;  // [B][reps]; no other step output, no episode record
+  out->q = ProbeArgs{};
+  PlayoutArgs& p = out->q.p;
+  p.key0 = sample_sm(io->seed);
+  p.ticket = io->ticket;
+  p.def_idle = io->def_idle; p.atk_idle = io->atk_idle;
+  p.steps_run = io->steps_run; p.first_def = io->first_def; p.first_atk = io->first_atk;
+  out->q.reps = io->reps;
+  return 0;
+}
+
+// The kernel with one timing pair and nothing else: state is only read, so no refill, no ring
+// guard, no launch counted, the observation ledger left alone (as the masks and the sampler).
+// ids == nullptr: every board.
+hipError_t launch_probe_call(const ProbeCall& c, const int32_t* ids, int cap, const int32_t* count,
+                             const td_list_status* verdict, hipStream_t s) {
+  ProbeArgs q = c.q;
+  q.p.ids = ids; q.p.cap = cap; q.p.count = count; q.p.verdict = verdict;
+  const EvPair ev = next_timing_pair(c.h);  // whatever `every` is (as the list calls')
+  return launch_probe(c.a, q, cap, s, ev.e0, ev.e1);
+}
+
+}  // namespace
+
+// One kernel on the step's stream; nothing is waited for, nothing of the handle is written.
+int td_probe(td_handle* h, const td_probe_io* io, void* stream) {
+  ProbeCall c;
+  if (check_probe_io("td_probe", h, io, &c)) return -1;
+  HIP_OK(launch_probe_call(c, nullptr, h->B, nullptr, nullptr, (hipStream_t)stream));
+  return 0;
+}
+
+// The boards named, every other output row left as it is.
+int td_probe_boards(td_handle* h, const td_probe_io* io, const int32_t* boards, int n, void* stream) {
+  return read_boards("td_probe_boards", check_probe_io, launch_probe_call, h, io, boards, n, stream);
+}
+
+int td_probe_boards_dev(td_handle* h, const td_probe_io* io, const int32_t* boards_dev, int cap, const int32_t* count_dev,
+                        td_list_status* status_dev, void* stream) {
+  return read_boards_dev("td_probe_boards_dev", check_probe_io, launch_probe_call, h, io, boards_dev, cap, count_dev,
+                         status_dev, stream);
+}
+
+const char* td_probe_kernel_name(td_handle* h) {
+  if (!h) return "";
+  StepArgs a = base_args(h);
+  a.multi = 0;  // (a multi-action handle is refused: the discrete row's name)
+  return kept_name(h, NAME_PROBE, kernel_display_name(probe_row(a)));
 }
 
 // Both kernel-kind setters: the kind is checked against the map side (td_kernel_choice.h

@@ -142,6 +142,18 @@ struct PlayoutArgs {
 // The playout unit's row (td_playout.hip): one kernel per (side, mode), no SCAN parameter.
 KernelRow playout_row(const StepArgs& a);
 
+// What a probe kernel takes beside its StepArgs (td_probe, td_probe_boards[_dev]; td_probe.h):
+// the playout's call and entries, and the replicas per entry.  Replica r of board b is the playout
+// at ticket p.ticket + r * steps (steps: StepArgs::frame_skip), and its outputs are row
+// b * reps + r of [B][reps] buffers: StepArgs::reward / done / win and p's steps_run, first_def,
+// first_atk.  Every other output pointer of the StepArgs is unused.
+struct ProbeArgs {
+  PlayoutArgs p;
+  int reps;
+};
+// The probe unit's row (td_probe.hip): one kernel per (side, mode), no SCAN parameter.
+KernelRow probe_row(const StepArgs& a);
+
 // TDGymBasic.reset for the boards in a.reset_mask (nullptr = all); failures in a.reset_fail.
 hipError_t launch_reset(const StepArgs& a, hipStream_t s);
 // random_agent=False with auto-reset: reset the boards the step just finished (a.done),

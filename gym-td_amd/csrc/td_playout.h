@@ -29,7 +29,8 @@
 //
 // What belongs here: playout_board and the kernels' body.  The kernels and their rows are
 // td_playout.hip's; skip_board and step_board share no text with this path beyond the pieces it
-// calls.
+// calls.  The probes (td_probe.h) run playout_board with PROBE set: the same sub-steps on a board
+// that is only read.
 #pragma once
 #include "td_list_dev.h"
 #include "td_mask.h"
@@ -111,11 +112,17 @@ __device__ __forceinline__ int playout_attacker(const U& u, const Ctx& x, uint64
   return __builtin_ctz(m);
 }
 
-template <int NC, int LT, int MODE>
+// PROBE (td_probe.h): the same sub-steps on a board that is only read.  The opponent's stream runs
+// on `mt`, the wave's private copy of the board's 624 words (its lazy twists land there), the
+// outputs go to row `row` of the caller's [B][reps] buffers, and nothing of the handle is written:
+// no reset, no flag, no board, stream or episode store.
+template <int NC, int LT, int MODE, bool PROBE = false>
 __device__ __forceinline__ void playout_board(Smem<NC>& S, uint32_t* raw, const Ctx& x, const StepArgs& a,
-                                              const PlayoutArgs& p, int b, const Prefetch& P) {
+                                              const PlayoutArgs& p, int b, const Prefetch& P, uint32_t* mt = nullptr,
+                                              int row = 0) {
   const TdDevCfg& C = x.C;
-  uint32_t* const opp = a.opp_mt + (size_t)b * OPP_WORDS;
+  uint32_t* const opp = PROBE ? mt : a.opp_mt + (size_t)b * OPP_WORDS;
+  const int o = PROBE ? row : b;  // the outputs' row
   uint32_t* const hot = a.opp_hot + (size_t)b * HOT_WORDS;
   U u;
   load_board<NC, PF_LARGE, PF_LARGE>(S, u, x, a, b, P);
@@ -127,18 +134,22 @@ __device__ __forceinline__ void playout_board(Smem<NC>& S, uint32_t* raw, const 
   if (!mask_board_live(u.num_roads)) {
     // never reset (its road generation failed): nothing to play, every output defined
     if (x.lane == 0) {
-      a.hdr[b].flags = u.flags | FLAG_NO_LAYOUT;
-      a.reward[b] = 0.0;
-      a.done[b] = 1;
-      if (p.steps_run) p.steps_run[b] = 0;
-      if (a.win) a.win[b] = -1;
+      if (!PROBE) a.hdr[b].flags = u.flags | FLAG_NO_LAYOUT;
+      a.reward[o] = 0.0;
+      a.done[o] = 1;
+      if (p.steps_run) p.steps_run[o] = 0;
+      if (a.win) a.win[o] = -1;
+      if (PROBE) {
+        if (p.first_def) p.first_def[o] = empty_def;
+      } else {
       if (a.allow_next) a.allow_next[b] = 0;
       if (a.cooldowns) a.cooldowns[b] = 0;
       if (a.ep_return) a.ep_return[b] = 0.0;
       if (a.ep_len) a.ep_len[b] = 0;
       if (p.first_def) p.first_def[b] = empty_def;  // what the sampler gives such a board
+      }
     }
-    if (p.first_atk && x.lane < 24) p.first_atk[(size_t)b * 24 + x.lane] = 4;
+    if (p.first_atk && x.lane < 24) p.first_atk[(size_t)o * 24 + x.lane] = 4;
     return;
   }
 
@@ -162,9 +173,9 @@ __device__ __forceinline__ void playout_board(Smem<NC>& S, uint32_t* raw, const 
     if (MODE != MODE_ATK) act_def = playout_defender(S, u, x, key, ub, p.def_idle);
     if (MODE != MODE_DEF) act_atk = playout_attacker(u, x, key, ub, p.atk_idle);
     if (j == 0) {
-      if (MODE != MODE_ATK && p.first_def && x.lane == 0) p.first_def[b] = act_def >= 0 ? (int64_t)((act_def >> 10) * x.NCr + (act_def & 1023)) : empty_def;
+      if (MODE != MODE_ATK && p.first_def && x.lane == 0) p.first_def[o] = act_def >= 0 ? (int64_t)((act_def >> 10) * x.NCr + (act_def & 1023)) : empty_def;
       if (MODE != MODE_DEF && p.first_atk && x.lane < 24)
-        p.first_atk[(size_t)b * 24 + x.lane] =
+        p.first_atk[(size_t)o * 24 + x.lane] =
             act_atk >= 0 && x.lane == (act_atk >> 2) * 8 ? (int64_t)(act_atk & 3) : (int64_t)4;
     }
     // ---- defender (step_board: legal by construction, FailCode 0)
@@ -178,9 +189,17 @@ __device__ __forceinline__ void playout_board(Smem<NC>& S, uint32_t* raw, const 
       wsync();
     }
     // ---- the built-in opponent
-    if (MODE == MODE_DEF) with_opp_rng(a, b, x.lane, R, [&](auto& G) { opponent_enemy(S, u, x, G, a.difficulty); });
-    if (MODE == MODE_ATK && raw_cells)
-      with_opp_rng(a, b, x.lane, R, [&](auto& G) { opponent_tower(S, u, x, G, a.difficulty); });
+    // (a probe: the board's own stream only -- random_agent = 0 is refused, and its branch would
+    // store to the layout stream)
+    if constexpr (PROBE) {
+      OppRng<false> G{R, R};
+      if (MODE == MODE_DEF) opponent_enemy(S, u, x, G, a.difficulty);
+      if (MODE == MODE_ATK && raw_cells) opponent_tower(S, u, x, G, a.difficulty);
+    } else {
+      if (MODE == MODE_DEF) with_opp_rng(a, b, x.lane, R, [&](auto& G) { opponent_enemy(S, u, x, G, a.difficulty); });
+      if (MODE == MODE_ATK && raw_cells)
+        with_opp_rng(a, b, x.lane, R, [&](auto& G) { opponent_tower(S, u, x, G, a.difficulty); });
+    }
     // the towers and map[6] are final for this sub-step: the raw words aside, then packed
     if (raw_cells) {
       skip_copy_cells<NC>(raw, S.cell, x.NCr, x.lane);
@@ -206,6 +225,16 @@ __device__ __forceinline__ void playout_board(Smem<NC>& S, uint32_t* raw, const 
   if (done) {
     if (MODE == MODE_ATK) win = u.base_LP <= 0 ? 1 : 0;
     else win = u.base_LP > 0 ? 1 : 0;
+  }
+  if constexpr (PROBE) {
+    // the outputs only: the board, its stream, its episode records and its layouts stay as they are
+    if (x.lane == 0) {
+      sst(&a.reward[o], total);
+      sst(&a.done[o], (uint8_t)(done ? 1 : 0));
+      if (a.win) sst(&a.win[o], win);
+      if (p.steps_run) sst(&p.steps_run[o], (int32_t)j);
+    }
+    return;
   }
   const uint8_t allow = (uint8_t)((u.atk_cd <= 1 ? 1 : 0) | (u.def_cd <= 1 ? 2 : 0));
   const int acd = u.atk_cd < 15 ? u.atk_cd : 15, dcd = u.def_cd < 15 ? u.def_cd : 15;

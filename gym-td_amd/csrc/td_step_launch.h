@@ -145,6 +145,16 @@ inline hipError_t launch_playout(const StepArgs& a, const PlayoutArgs& p, int gr
   return launch_row(playout_row(a), grid, args, s, ev0, ev1);
 }
 
+// Probes (td_probe, td_probe_boards[_dev]): q.reps playouts of a.frame_skip sub-steps for each of the
+// entries q.p names, one block per (entry, replica) of `entries` (a.B, the list's n or cap).
+inline hipError_t launch_probe(const StepArgs& a, const ProbeArgs& q, int entries, hipStream_t s,
+                               hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr) {
+  const long long grid = (long long)entries * q.reps;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;  // (the kernel's wave index is an int)
+  void* args[] = {const_cast<StepArgs*>(&a), const_cast<ProbeArgs*>(&q)};
+  return launch_row(probe_row(a), (int)grid, args, s, ev0, ev1);
+}
+
 // Small-batch step-kernel workgroups (one per board) resident at once on `cus` compute units:
 // the batch size up to which a step runs as one round of waves of the one-wave (waves = 1,
 // td_step_kernel_small) or two-wave (td_step_kernel_small2) kernel of the format a.obs_f16.

@@ -22,6 +22,7 @@ STEP_KERNELS = {"auto": 0, "large": 1, "small": 2, "small2": 3}  # enum td_step_
 OBS_F32, OBS_F16 = 0, 1  # enum td_obs_format
 MAX_FRAME_SKIP = 16  # TD_MAX_FRAME_SKIP
 MAX_PLAYOUT_STEPS = 4096  # TD_MAX_PLAYOUT_STEPS
+MAX_PROBE_REPS = 256  # TD_MAX_PROBE_REPS
 
 c_u32p = ctypes.POINTER(ctypes.c_uint32)
 c_i32p = ctypes.POINTER(ctypes.c_int32)
@@ -117,6 +118,20 @@ class TdPlayoutIO(ctypes.Structure):
         super().__init__(**kw)
 
 
+class TdProbeIO(ctypes.Structure):
+    """struct td_probe_io (tdstep.h): the size / ABI header, the sub-steps and the replicas, the
+    sampler's idle probabilities, seed and ticket, then the device outputs ([B][reps])."""
+    _fields_ = [("size", ctypes.c_uint32), ("abi", ctypes.c_uint32), ("steps", ctypes.c_int32),
+                ("reps", ctypes.c_int32), ("def_idle", ctypes.c_uint32), ("atk_idle", ctypes.c_uint32),
+                ("seed", ctypes.c_uint64), ("ticket", ctypes.c_uint64)] + [(n, c_vp) for n in (
+                    "reward", "done", "steps_run", "win", "first_def", "first_atk")]
+
+    def __init__(self, **kw):
+        kw.setdefault("size", ctypes.sizeof(TdProbeIO))
+        kw.setdefault("abi", ABI_VERSION)
+        super().__init__(**kw)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError("libtdstep.so not found at %s -- build it with `make -C gym-td_amd/csrc` "
@@ -174,6 +189,11 @@ def _load():
         "td_playout_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp, ctypes.c_int, c_vp]),
         "td_playout_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdPlayoutIO), c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
         "td_playout_kernel_name": (ctypes.c_char_p, [c_vp]),
+        "td_probe_io_init": (None, [ctypes.POINTER(TdProbeIO)]),
+        "td_probe": (ctypes.c_int, [c_vp, ctypes.POINTER(TdProbeIO), c_vp]),
+        "td_probe_boards": (ctypes.c_int, [c_vp, ctypes.POINTER(TdProbeIO), c_vp, ctypes.c_int, c_vp]),
+        "td_probe_boards_dev": (ctypes.c_int, [c_vp, ctypes.POINTER(TdProbeIO), c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+        "td_probe_kernel_name": (ctypes.c_char_p, [c_vp]),
         "td_layout_words": (ctypes.c_int, [ctypes.c_int]),
         "td_layout_from_roads": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i32p, c_i32p, c_u32p]),
         "td_layout_generate": (ctypes.c_int, [c_u32p, ctypes.c_int, ctypes.c_int, c_u32p]),

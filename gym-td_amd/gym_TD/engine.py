@@ -958,6 +958,93 @@ class TDEngine(object):
         'td_playout_kernel<10, 0>'."""
         return _lib.lib.td_playout_kernel_name(self._h).decode()
 
+    # ---------------------------------------------------------------- probes
+    def _probe_prepare(self, steps, reps, ticket, def_idle, atk_idle, first):
+        """The engine's probe buffers -- (B, reps), allocated on first use and again when ``reps``
+        grows -- as a td_probe_io for this call's ticket, and the tickets the call takes of the
+        engine's sampling counter: ``ticket=None`` starts at the counter, which advances by
+        ``steps * reps`` once the call is accepted; a refused call takes none."""
+        B = self.B
+        steps, reps = int(steps), int(reps)
+        width = min(max(reps, 1), _lib.MAX_PROBE_REPS)  # (a refused reps still gets buffers; the call writes none)
+        buf = getattr(self, "_probe_buf", None)
+        if buf is None or buf["width"] < width:
+            z = lambda dt: torch.zeros(B * width, dtype=dt, device=self.device)  # noqa: E731
+            buf = self._probe_buf = {"width": width, "reward": z(torch.float64), "done": z(torch.uint8),
+                                     "steps_run": z(torch.int32), "win": z(torch.int8), "first_def": None,
+                                     "first_atk": None}
+        if first:
+            if self.mode != "atk" and buf["first_def"] is None:
+                buf["first_def"] = torch.full((B * buf["width"],), 6 * self.L * self.L, dtype=torch.int64,
+                                              device=self.device)
+            if self.mode != "def" and buf["first_atk"] is None:
+                buf["first_atk"] = torch.full((B * buf["width"], 3, 8), 4, dtype=torch.int64, device=self.device)
+        advance = 0  # the counter moves once the library has accepted the call (_playout_done)
+        if ticket is None:
+            ticket, advance = self._sample_ticket, steps * reps
+        io = _lib.TdProbeIO(steps=steps, reps=reps, seed=self.sample_seed, ticket=int(ticket) & sampling.M64,
+                            def_idle=sampling.idle_units(def_idle), atk_idle=sampling.idle_units(atk_idle))
+        out = {}
+        for name in ("reward", "done", "steps_run", "win", "first_def", "first_atk"):
+            t = buf[name] if first or not name.startswith("first") else None
+            if t is not None:  # the first B * reps rows of the flat buffer, as [B][reps]
+                t = t[:B * width].view((B, width) + tuple(t.shape[1:]))
+            out[name] = t
+            setattr(io, name, t.data_ptr() if t is not None else None)
+        return io, out, advance
+
+    def probe(self, steps, reps, boards=None, ticket=None, def_idle=0.0, atk_idle=0.0, first=False):
+        """``reps`` independent random playouts per board, the boards left untouched (td_probe,
+        td_probe_boards): every board -- or the boards named in ``boards``, under
+        ``step_boards``' rules -- is only read.  Replica r of board b is what
+        ``playout(steps, [b], ticket + r * steps)`` would return on the board's present state
+        (``gym_TD.sampling.reference_probe`` states it on the CPU); every replica starts from the
+        same position of the board's opponent stream, so replicas differ through the sampled side
+        only.  A replica stops after the sub-step that ends its episode; nothing is reset.
+
+        Returns a dict of the engine's own (B, reps) device tensors, indexed by board id, then
+        replica (allocated on first use, again when ``reps`` grows; only the named boards' rows are
+        overwritten by the next call): ``"reward"`` float64, ``"done"`` uint8, ``"steps_run"``
+        int32, ``"win"`` int8, and with ``first`` ``"first_def"`` int64 (B, reps) / ``"first_atk"``
+        int64 (B, reps, 3, 8) (None without ``first`` and for a side the mode lacks).
+        ``ticket=None`` takes the engine's sampling counter and advances it by ``steps * reps`` (a
+        refused call takes none).  No board, stream, flag, episode record, staged layout or
+        observation byte changes, and a retained observation stays known: the next ``step()``
+        skips as if no probe had run.  One kernel on torch's current stream, which must be the
+        stream of step(); nothing is synchronised.
+        TDError, nothing changed: ``steps`` outside 1 .. 4096, ``reps`` outside 1 .. 256,
+        multi-action, random_agent=False, an id out of range or named twice."""
+        io, out, advance = self._probe_prepare(steps, reps, ticket, def_idle, atk_idle, first)
+        if boards is None:
+            self._playout_done(_lib.lib.td_probe(self._h, io, self._stream()), advance)
+        else:
+            ids = _board_ids(boards)
+            self._playout_done(_lib.lib.td_probe_boards(self._h, io, ids.ctypes.data, int(ids.size), self._stream()),
+                               advance)
+        return out
+
+    def probe_boards_dev(self, boards, steps, reps, count=None, status=None, ticket=None, def_idle=0.0, atk_idle=0.0,
+                         first=False):
+        """``probe`` for ids that are on the device (td_probe_boards_dev): nothing is copied to the
+        host or waited for.  ``boards``, ``count`` and ``status`` as in ``step_boards_dev``; a list
+        the device refuses writes no byte (``list_errors()``).  The tensors stay alive until the
+        next call."""
+        ids = _dev_ids(boards, self.device, "probe")
+        c = _dev_words(count, 1, self.device, "count")
+        st = _dev_words(status, 4, self.device, "status")
+        io, out, advance = self._probe_prepare(steps, reps, ticket, def_idle, atk_idle, first)
+        self._playout_done(_lib.lib.td_probe_boards_dev(self._h, io, ids.data_ptr(), int(ids.numel()),
+                                                        c.data_ptr() if c is not None else None,
+                                                        st.data_ptr() if st is not None else None, self._stream()),
+                           advance)
+        self._keep_probe_list = (ids, c, st)  # alive until the next call's kernels are behind them on the stream
+        return out
+
+    def probe_kernel_name(self):
+        """The kernel the three probe calls launch (td_probe_kernel_name), e.g.
+        'td_probe_kernel<10, 0>'."""
+        return _lib.lib.td_probe_kernel_name(self._h).decode()
+
     def _changed(self, rows=None):
         """Called in front of every call that can change a board or the config: the state
         serial advances.  rows: the boards the call can change, ``("host", int32 array)`` or

@@ -478,6 +478,21 @@ class TDVecEnv(object):
             self._masks = self.engine.refresh_action_mask()
         return out["reward"], out["done"], out["steps_run"]
 
+    def probe(self, steps, reps, boards=None, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """``reps`` random playouts per env, or per env named in ``boards``, with the envs left as
+        they are (TDEngine.probe): the value estimate of a state.  Returns (returns, dones,
+        lengths): the engine's (num_envs, reps) device tensors ``reward`` float64, ``done`` uint8
+        and ``steps_run`` int32, the named rows fresh.  No state changes, so with
+        ``action_mask=True`` no mask is recomputed and none goes stale."""
+        out = self.engine.probe(steps, reps, boards, ticket, def_idle, atk_idle)
+        return out["reward"], out["done"], out["steps_run"]
+
+    def probe_dev(self, boards, steps, reps, count=None, status=None, ticket=None, def_idle=0.0, atk_idle=0.0):
+        """probe() for env ids that are on the device (TDEngine.probe_boards_dev).  ``count`` /
+        ``status`` as in fork_dev()."""
+        out = self.engine.probe_boards_dev(boards, steps, reps, count, status, ticket, def_idle, atk_idle)
+        return out["reward"], out["done"], out["steps_run"]
+
     def _step(self, actions, run, partial=False):
         if self.mode == "def":
             obs, rew, done = run(def_act=actions)

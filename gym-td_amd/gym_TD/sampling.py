@@ -93,6 +93,19 @@ def reference_playout(env, state_of, L, cfg, hp, mode, seed, ticket, b, steps, d
             "info": info, "events": events}
 
 
+def reference_probe(env, steps, reps, state_of, L, cfg, hp, mode, seed, ticket, b, def_idle=0, atk_idle=0, cap=True):
+    """The CPU statement of ``TDEngine.probe`` for one board: replica r (0 <= r < ``reps``) is
+    ``reference_playout`` at ticket + r * steps (mod 2^64) on a deep copy of ``env`` -- its state
+    and its opponent's stream as they are now, so every replica starts from the same stream
+    position --, and ``env`` itself is never stepped.  The other arguments are
+    ``reference_playout``'s.  Returns the list of the replicas' dicts."""
+    import copy
+    steps = int(steps)
+    return [reference_playout(copy.deepcopy(env), state_of, L, cfg, hp, mode, seed, (int(ticket) + r * steps) & M64, b,
+                              steps, def_idle, atk_idle, cap)
+            for r in range(int(reps))]
+
+
 def reference_sample(def_mask, atk_mask, seed, ticket, b, def_idle, atk_idle, L, multi):
     """(def_act, atk_act, def_count, atk_count) of board b, in the step's formats.
 

@@ -772,6 +772,68 @@ int td_playout_boards_dev(td_handle* h, const td_playout_io* io, const int32_t* 
  * for a generic side, mode).  The string is the handle's, valid until the next call. */
 const char* td_playout_kernel_name(td_handle* h);
 
+/* Probes: `reps` independent random playouts of every board in ONE launch, from the board's
+ * present state, which is only read -- what a search does to estimate the value of a state.  No
+ * scratch boards, no copy, nothing of the handle changed.  Defined by a call the library already
+ * has.  Replica r (0 <= r < reps) of board b is this hypothetical call:
+ *   td_playout_boards of board b with the same seed, def_idle, atk_idle and steps, at ticket
+ *     ticket + r * steps (mod 2^64), on the board's present state, its effects on the handle
+ *     discarded.
+ * The replica's reward, done, steps_run, win, first_def and first_atk are that call's outputs.
+ * Sub-step j of replica r draws at ticket + r * steps + j; the key is the board id, as in the
+ * sampler.  So replica 0 is td_playout_boards at `ticket`, output for output; no two replicas of
+ * one call share a ticket; the call takes steps * reps tickets.
+ *   Every replica of a board starts from the same position of the board's opponent stream (TD-def,
+ *     TD-atk): each runs the built-in opponent on a private copy of the stream's words.  The
+ *     replicas differ through the sampled side only; where the sampled side has one legal move
+ *     throughout, they are the same playout.
+ *   A replica stops after the sub-step that ends its episode.  No reset happens and no staged
+ *     layout is consumed; TD_FLAG_NO_LAYOUT is never set; auto-reset on or off makes no difference.
+ *   A board never reset gets, for every replica, reward 0, done 1, steps_run 0, win -1, first_def
+ *     the no-op and first_atk all 4.  Its header flag is not written.
+ * After the call none of these differs from before it: the exported state of any board; either
+ * stream, down to the raw MT words, the lazy-twist boundary and the hot record; the flags,
+ * td_episode_stats and td_episode_records; the layout rings and their heads; the step count of
+ * the refill cadence and the ring guard; the observation buffer and what td_retain_obs knows of
+ * it (the next retained step skips as if no probe had run); every output row of td_step and
+ * td_playout.  The call may take the next td_kernel_timing pair, and in the device-list form the
+ * next list-check serial and a td_list_errors count.  Nothing else of the handle changes.
+ * Outputs, each of full-batch shape [B][reps] (first_atk [B][reps][3][8]) and indexed by board
+ * id, then replica; only the rows of the boards named are written; reward and done are
+ * required, every other pointer may be NULL.
+ * Asynchronous on `stream`, which must be the step's stream; nothing is waited for.
+ * Refused (< 0, a whole message in td_last_error, nothing enqueued, nothing changed), in this
+ * order: a NULL io; a bad size / abi word; a NULL handle; steps outside
+ * [1, TD_MAX_PLAYOUT_STEPS]; reps outside [1, TD_MAX_PROBE_REPS]; a missing reward or done;
+ * first_def on TD-atk or first_atk on TD-def; a multi-action handle; random_agent = 0.
+ * td_frame_skip() plays no part.
+ * td_probe_boards / td_probe_boards_dev -- the boards a list names, under td_playout_boards /
+ *   td_playout_boards_dev's contracts word for word: a board named twice is refused (replication
+ *   is what reps is for), and a refused device list writes nothing. */
+#define TD_MAX_PROBE_REPS 256
+typedef struct td_probe_io {
+  uint32_t size, abi;          /* checked first, as td_playout_io */
+  int32_t steps;               /* sub-steps per replica, 1 .. TD_MAX_PLAYOUT_STEPS */
+  int32_t reps;                /* replicas per board, 1 .. TD_MAX_PROBE_REPS */
+  uint32_t def_idle, atk_idle; /* td_sample_io's, in units of 2^-32 */
+  uint64_t seed, ticket;       /* td_sample_io's; sub-step j of replica r draws at ticket + r * steps + j */
+  double* reward;              /* [B][reps] */
+  uint8_t* done;               /* [B][reps] */
+  int32_t* steps_run;          /* [B][reps] */
+  int8_t* win;                 /* [B][reps] */
+  int64_t* first_def;          /* [B][reps] */
+  int64_t* first_atk;          /* [B][reps][3][8] */
+} td_probe_io;
+/* Zero *io and set its size / abi words. */
+void td_probe_io_init(td_probe_io* io);
+int td_probe(td_handle* h, const td_probe_io* io, void* stream);
+int td_probe_boards(td_handle* h, const td_probe_io* io, const int32_t* boards, int n, void* stream);
+int td_probe_boards_dev(td_handle* h, const td_probe_io* io, const int32_t* boards_dev, int cap,
+                        const int32_t* count_dev, td_list_status* status_dev, void* stream);
+/* The kernel the three calls launch, as rocprofv3 shows it: "td_probe_kernel<10, 0>" (L or 0 for
+ * a generic side, mode).  The string is the handle's, valid until the next call. */
+const char* td_probe_kernel_name(td_handle* h);
+
 /* Which step kernel td_step launches (one wave per board in all three; they differ in
  * occupancy and load schedule, not in results):
  *   TD_KERNEL_LARGE  td_step_kernel        several rounds of waves (7 per SIMD), live slots
